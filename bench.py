@@ -11,13 +11,16 @@ MGPIS::CG_SOLV) + the interface-eliminated coarse-space correction (muscSett = 2
 DEHW's own setting, DEHW.h:2222, 2239) + the interface step + MONITOR.  The global problem is fixed and its subdomains
 are spread over the ranks (strong scaling); N = 1 runs all 8 on one MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Rank 0 prints one JSON line.  `roofline` is the fine-level SELL-BSR3 SpMV kernel (the dominant
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the line;
+`--dump-outputs DIR` also writes what the last timed step computed (DIR/<name>.npy).  `--full` adds
+the measurements that take runs of their own: the general-mesh line (a child process), the STREAM
+ceiling and `cpu_baseline`.  `roofline` is the fine-level SELL-BSR3 SpMV kernel (the dominant
 kernel family, one launch covers every owned subdomain), timed by HIP events around its launch in
 the eager first PCG iteration of every batched solve, on the solve stream;
-`cpu_baseline` is the CPU port (oracle/cpu_admm.py: SGS-faithful MGPIS + the interface step) pricing
+`cpu_baseline` (`--full`) is the CPU port (oracle/cpu_admm.py: SGS-faithful MGPIS + the interface step) pricing
 one full ADMM iteration of the same workload at the device run's final state.
 """
 from __future__ import annotations
@@ -32,6 +35,7 @@ import time
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
+T_START = time.perf_counter()
 sys.path.insert(0, str(ROOT))
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
@@ -84,13 +88,21 @@ def parse():
     ap.add_argument("--uneven", action="store_true",
                     help="group g (1 + g mod 3) times --nx cells long: subdomains of three sizes, packed onto the "
                          "ranks by LPT (partition.owner_for) as DEHW's uneven subdomains (not the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the general-mesh line, the STREAM "
+                         "ceiling and cpu_baseline (each can be dropped again by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results as DIR/<name>.npy (float64; see dump_outputs)")
     ap.add_argument("--no-general", action="store_true",
-                    help="skip the general-mesh line the N = 1 headline run adds (a child process, before the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-stream-ceiling", action="store_true", help="skip the same-process STREAM ceiling")
+                    help="with --full: skip the general-mesh line the N = 1 headline run adds (a child process, before the headline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-stream-ceiling", action="store_true", help="with --full: skip the same-process STREAM ceiling")
     ap.add_argument("--traffic-json", default=os.environ.get("DDPCA_TRAFFIC_JSON", str(ROOT / "profiles" / "traffic.json")),
                     help="PMC-derived HBM bytes per launch of the roofline kernel (profiles/make_traffic.py)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:
+        a.no_general = a.no_cpu_baseline = a.no_stream_ceiling = True
+    return a
 
 
 def main():
@@ -128,6 +140,7 @@ def main():
                            ip_contact=a.ip_contact, ip_glued=a.ip_glued, uneven=int(a.uneven), **feat)
     nip = sum(len(P.array("ip_w", ts)) for ts in range(P.nint))
     nsub = P.nsub
+    log(rank, "mesh and integration points built")
     # contiguous blocks for equal subdomains (worm/wheel pairs stay together), LPT by node count
     # when the sizes differ (--uneven; DEHW's 52 subdomains)
     owner = part.owner_for([len(P.array("coords", tv)) // 3 for tv in range(nsub)], world)
@@ -140,6 +153,7 @@ def main():
     if a.musc:
         P.set_coarse(a.musc, [a.dole] * nsub)
     P.ESTABLISH(owner, rank)
+    log(rank, "operators established")
     mc = D.MCONTACT(P, device=local, rank=rank, nranks=world, owner=owner, smoother=a.smoother, nu=a.nu,
                     omega=-a.omega_scale, coarse_level=a.coarse_level,
                     iters_per_graph=a.iters_per_graph, warm_start=a.warm_start, precond_fp32=a.precond_fp32,
@@ -166,6 +180,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     log(rank, f"{n} ADMM iterations in {elapsed:.3f} s")
+    if a.dump_outputs:
+        dump_outputs(Path(a.dump_outputs), mc, P, owner, rank, world, n)
     tm = mc.timing()
     by = mc.bytes()  # algorithmic bytes of the timed iterations per phase (mcontact_gpu_bytes)
     phases = list(mc.BYTE_PHASES)
@@ -317,16 +333,64 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+    log(rank, "device state released")
     if result is not None:
         print(json.dumps(result), flush=True)
+    del P
+    log(rank, "host problem released")
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of float64 values over all files of a run (all ranks together)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out: Path, mc, P, owner, rank: int, world: int, n: int) -> None:
+    """What a caller of CONTACT_ANALYSIS holds after the last timed step, as float64 .npy files:
+    resuDisp_<tv> (displacements of every subdomain this rank owns), inpoGamm_<ts> (the contact
+    tractions at the integration points of every interface it handles), inteAuxi_<2 ts + s> /
+    inteLagr_<2 ts + s> (auxiliary variable and multiplier of every interface side it owns) and
+    resuMoni (the MONITOR rows of the n timed steps).  The files of one run share DUMP_BUDGET_BYTES
+    equally: an array longer than its share is written as a fixed sample -- the entries at sorted
+    indices drawn without replacement by numpy's default_rng([DUMP_SEED, length]) -- so the same
+    arguments give the same entries of the same arrays from run to run and from build to build."""
+    import numpy as np
+    D = importlib.import_module("ddpca-admm_amd")
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    for tv in range(P.nsub):
+        if owner[tv] == rank:
+            arrays[f"resuDisp_{tv}"] = mc.get("resuDisp", tv)
+    for ts in range(P.nint):
+        try:
+            arrays[f"inpoGamm_{ts}"] = mc.get("inpoGamm", ts)
+        except D.DdpcaError:  # handled by another rank
+            pass
+        for s in range(2):
+            try:
+                arrays[f"inteAuxi_{2 * ts + s}"] = mc.get("inteAuxi", 2 * ts + s)
+                arrays[f"inteLagr_{2 * ts + s}"] = mc.get("inteLagr", 2 * ts + s)
+            except D.DdpcaError:  # a side of another rank's subdomain
+                pass
+    if rank == 0:
+        arrays["resuMoni"] = mc.monitor()[-n:]
+    share = DUMP_BUDGET_BYTES // 8 // max(world, 1) // max(len(arrays), 1)
+    total = 0
+    for name, v in arrays.items():
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        if v.size > share:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, v.size]).choice(v.size, share, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(out / f"{name}.npy", v)
+        total += v.nbytes
+    log(rank, f"wrote {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {out}")
 
 
 def run_general_child(a) -> dict:
     """The general-mesh line: bench.py --mesh general in a child process (DDPCA_LATTICE=0), same
     workload size, steps and warmup; its JSON object, or the failure."""
     import subprocess
-    cmd = [sys.executable, str(Path(__file__).resolve()), "--mesh", "general", "--no-general", "--no-cpu-baseline",
-           "--no-stream-ceiling", "--steps", str(a.steps), "--warmup", str(a.warmup), "--groups", str(a.groups),
+    cmd = [sys.executable, str(Path(__file__).resolve()), "--mesh", "general",
+           "--steps", str(a.steps), "--warmup", str(a.warmup), "--groups", str(a.groups),
            "--nx", str(a.nx), "--ny", str(a.ny), "--nz", str(a.nz), "--gl", str(a.gl), "--fric", str(a.fric),
            "--ip-contact", str(a.ip_contact), "--ip-glued", str(a.ip_glued),
            # precond_fp32 = 4: the colour sweeps' fp32 copy needs lattice fine transfers without band
@@ -354,7 +418,7 @@ def run_general_child(a) -> dict:
 def log(rank: int, msg: str) -> None:
     """Progress on stderr (stdout carries the one JSON line)."""
     if rank == 0:
-        print(f"[bench] {msg}", file=sys.stderr, flush=True)
+        print(f"[bench +{time.perf_counter() - T_START:.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
 def traffic_key(a) -> dict:

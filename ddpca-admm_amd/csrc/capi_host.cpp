@@ -452,7 +452,18 @@ int ddpca_problem_establish_owned(ddpca_problem_t h, const int32_t* owner, int r
 }
 
 int ddpca_problem_destroy(ddpca_problem_t h) {
-    delete reinterpret_cast<Problem*>(h);
+    Problem* P = reinterpret_cast<Problem*>(h);
+    if (P) {
+        // an established problem holds tens of GB, nearly all of it in the subdomains and the
+        // interfaces: they are released side by side (seconds at the end of a run otherwise)
+        const int64_t nsub = (int64_t)P->mc.multGrid.size(), nint = (int64_t)P->mc.searCont.size();
+#pragma omp parallel for schedule(dynamic, 1)
+        for (int64_t i = 0; i < nsub + nint; ++i) {
+            if (i < nsub) P->mc.multGrid[i] = MULTIGRID();
+            else P->mc.searCont[i - nsub] = Interface();
+        }
+    }
+    delete P;
     return DDPCA_OK;
 }
 

@@ -1909,7 +1909,28 @@ void build(ddpca_mcontact& H, Problem& P) {
     }
     // ---- interface operators over W (MCONTACT.h:2632-2636, 2671-2704)
     {
-        Rows rg(H.G), ra(H.R), rl(H.R), rg1;
+        // fused update when the penalty operators are exact multiples of the plain ones
+        // (entries agree to rounding: the penalty operators are accumulated with pen inside the
+        // basis products, e.g. off-diagonal T^T P T entries are rounding noise around 0)
+        auto proportional = [](const Csr& A, const Csr& B, double rho) {
+            if (A.nrow != B.nrow || A.ptr != B.ptr || A.col != B.col) return false;
+            double amax = 0.0;
+            for (double v : A.val) amax = std::max(amax, std::abs(v));
+            for (int64_t k = 0; k < A.nnz(); ++k)
+                if (std::abs(A.val[k] - rho * B.val[k]) > 1e-13 * amax) return false;
+            return true;
+        };
+        const char* env = std::getenv("DDPCA_MASS_FUSED");
+        bool fuse = !H.sides.empty() && (!env || std::atoi(env) != 0);
+        for (const auto& sd : H.sides) {
+            const Interface& itf = mc.searCont[sd.ts];
+            const double rho = itf.penN;
+            fuse = fuse && itf.penN == itf.penF && rho > 0.0 && proportional(itf.inteMass_pena[sd.s], itf.inteMass[sd.s], rho) &&
+                   proportional(itf.systTran_pena[sd.s], itf.systTran[sd.s], rho);
+        }
+        // (the fused update applies op_wv instead of op_aux / op_lam: their rows are built only
+        // for the sequential update)
+        Rows rg(H.G), ra(fuse ? 0 : H.R), rl(fuse ? 0 : H.R), rg1;
         std::vector<int32_t> g1dst;
         std::map<int64_t, int64_t> g1off;  // rank-local SELL interface -> its first row in rg1
         std::vector<double> gc(H.G, 0.0);
@@ -1938,6 +1959,7 @@ void build(ddpca_mcontact& H, Problem& P) {
                 }
                 if (s == 0) gc[I.goff + i] = -0.5 * (itf.pemaDiag[i] * itf.inpoNgap[i]);
             }
+            if (fuse) continue;
             // aux RHS: systTran_pena^T u + inteMass lambda + inteInpo gamma
             const Csr tTp = transpose(itf.systTran_pena[s]);
             const Csr& M = itf.inteMass[s];
@@ -1962,8 +1984,10 @@ void build(ddpca_mcontact& H, Problem& P) {
             H.gam1.alloc(H.op_gamma1.nrow);
             H.gam1_dst.upload(g1dst);
         }
-        H.op_aux.build(ra);
-        H.op_lam.build(rl);
+        if (!fuse) {
+            H.op_aux.build(ra);
+            H.op_lam.build(rl);
+        }
         H.gcst.upload(gc);
         std::vector<const Csr*> Ma, Ml;
         std::vector<int64_t> ro;
@@ -1973,29 +1997,12 @@ void build(ddpca_mcontact& H, Problem& P) {
             Ml.push_back(&itf.inteMass[sd.s]);
             ro.push_back(sd.roff);
         }
+        // (built in the fused case too, where mb_wv solves instead: the iteration's check() and byte
+        // accounting walk all three batches, and the two cost 0.1 s at the headline size)
         H.mb_aux.build(Ma, ro, H.R);
         H.mb_lam.build(Ml, ro, H.R);
         H.mb_aux.set_split(two_streams());
         H.mb_lam.set_split(two_streams());
-        // fused update when the penalty operators are exact multiples of the plain ones
-        // (entries agree to rounding: the penalty operators are accumulated with pen inside the
-        // basis products, e.g. off-diagonal T^T P T entries are rounding noise around 0)
-        auto proportional = [](const Csr& A, const Csr& B, double rho) {
-            if (A.nrow != B.nrow || A.ptr != B.ptr || A.col != B.col) return false;
-            double amax = 0.0;
-            for (double v : A.val) amax = std::max(amax, std::abs(v));
-            for (int64_t k = 0; k < A.nnz(); ++k)
-                if (std::abs(A.val[k] - rho * B.val[k]) > 1e-13 * amax) return false;
-            return true;
-        };
-        const char* env = std::getenv("DDPCA_MASS_FUSED");
-        bool fuse = !H.sides.empty() && (!env || std::atoi(env) != 0);
-        for (const auto& sd : H.sides) {
-            const Interface& itf = mc.searCont[sd.ts];
-            const double rho = itf.penN;
-            fuse = fuse && itf.penN == itf.penF && rho > 0.0 && proportional(itf.inteMass_pena[sd.s], itf.inteMass[sd.s], rho) &&
-                   proportional(itf.systTran_pena[sd.s], itf.systTran[sd.s], rho);
-        }
         if (fuse) {
             H.fused = true;
             Rows rwv(2 * H.R);

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <atomic>
 #include <deque>
+#include <memory>
 #include <array>
 #include <climits>
 #include <cmath>
@@ -2319,13 +2320,14 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
         };
         const int64_t vc_nslot = nslot;
         if (!L.tbl && (l == nlev - 1 || !vc32)) {
-            std::vector<double> v64(val.size());
+            // (every element is written below: no serial zero fill of the level's largest array)
+            std::unique_ptr<double[]> v64(new double[val.size()]);
 #pragma omp parallel for schedule(static)
             for (int64_t q = 0; q < nslot; ++q)
                 for (int ij = 0; ij < 9; ++ij)
                     for (int64_t lane = 0; lane < kChunk; ++lane)
                         v64[q * 9 * kChunk + slot_elem<double>(ij, lane)] = val[(q * 9 + ij) * kChunk + lane];
-            L.val.upload(v64);
+            L.val.upload(v64.get(), val.size());
         }
         // levels in block-exponent fp16: the finest h16_levels (DDPCA_H16_LEVELS, default 3: +2 % over 1 under block
         // Jacobi, profiles/r01_sweep_h16.txt; with the multicolour fine level 3 over 2 +1.1 % at 8 subdomains,

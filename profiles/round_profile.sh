@@ -24,7 +24,7 @@ timeout -s KILL 240 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$VC" -d $
 python3 profiles/pmc_kernels.py $(find $OUT/pmc_vc_fetch -name "*counter_collection.csv" | head -1) $(find $OUT/pmc_vc_write -name "*counter_collection.csv" | head -1) --out $OUT/pmc_kernels.json > $OUT/pmc_kernels.txt 2>&1
 fi
 if [ "$MODE" != nobench ]; then
-timeout -k 10 1200 python3 -u bench.py > $OUT/bench.json.log 2>&1
+timeout -k 10 1200 python3 -u bench.py --full > $OUT/bench.json.log 2>&1
 fi
 if [ "$MODE" != benchonly ]; then
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-general > $OUT/trace.log 2>&1

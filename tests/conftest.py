@@ -1,6 +1,7 @@
 """Shared fixtures.  `-m gpu` tests need a gfx950 device and the built libddpca_amd.so; the
 rest run on CPU (oracle vs golden vectors, host operator pipeline, C-ABI exports)."""
 import importlib
+import os
 import sys
 from pathlib import Path
 
@@ -15,6 +16,12 @@ if str(ROOT) not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X (gfx950) GPU")
+    # the reference harnesses (oracle/_ref/ref_*) are child processes linked to libddpca_amd.so: they
+    # take this tree's library wherever they were built and wherever oracle/_ref itself lies (a
+    # link to another directory, a copy carried over from another checkout)
+    libdir = str(ROOT / "ddpca-admm_amd")
+    paths = [p for p in os.environ.get("LD_LIBRARY_PATH", "").split(os.pathsep) if p and p != libdir]
+    os.environ["LD_LIBRARY_PATH"] = os.pathsep.join([libdir] + paths)
 
 
 @pytest.fixture(scope="session")
