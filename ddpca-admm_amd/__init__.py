@@ -179,6 +179,16 @@ def _declare(L: C.CDLL) -> None:
     L.ddpca_write_resuDisp.argtypes = [C.c_char_p, _P, C.c_int64, C.c_int64, _P, _P]
     L.ddpca_write_resuCont.argtypes = [C.c_char_p, C.c_double, C.c_int64, _P, _P, _P]
     L.ddpca_write_resuMoni.argtypes = [C.c_char_p, _P, C.c_int64, C.c_int64]
+    L.ddpca_write_resuStre.argtypes = [C.c_char_p, _P, C.c_int64]
+    L.ddpca_multigrid_create.argtypes = [C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]
+    L.ddpca_multigrid_set.argtypes = [_P, C.c_char_p, C.c_int64, _P, _P]
+    L.ddpca_multigrid_build.argtypes = [_P, _P]
+    L.ddpca_multigrid_view.argtypes = [_P, C.c_char_p, C.c_int64, C.POINTER(_P), _I64P, C.POINTER(C.c_int)]
+    L.ddpca_multigrid_destroy.argtypes = [_P]
+    L.ddpca_multigrid_stress.argtypes = [_P, C.c_int, _P, _P]
+    L.mcontact_gpu_stress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64]
+    L.mcontact_gpu_stress.restype = C.c_int64
+    L.ddpca_stress_last_kernel_ms.argtypes = [_DP]
     L.mgpis_gpu_vcycle.argtypes = [_P, _P, _P]
     L.mgpis_gpu_info.argtypes = [_P, _I64P]
     L.mgpis_gpu_bench_spmv.argtypes = [_P, C.c_int, C.c_int, _DP, _DP]
@@ -625,6 +635,68 @@ class MULTIGRID:
         return u
 
 
+class TreeMultigrid:
+    """The MULTIGRID pipeline on a caller's element tree (ddpca_multigrid_*, include/ddpca_amd.h):
+    create from the tree arrays, ``set`` the inputs (nodeRota, material, ...), ``build``, then
+    ``view`` the operators and recover stresses with ``stress``.  Node ids are the caller's; after
+    ``build`` nodal vectors are in positions and ``posiNode`` maps them back."""
+
+    def __init__(self, coords, corner, parent=None, level=None, refiPatt=None, child_ptr=None, child=None):
+        xyz = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1, 3)
+        cn = np.ascontiguousarray(corner, dtype=np.int64).reshape(-1, 8)
+        ne = len(cn)
+        i64 = lambda a, d: np.ascontiguousarray(d if a is None else a, dtype=np.int64)  # noqa: E731
+        pa, lv = i64(parent, np.full(ne, -1)), i64(level, np.zeros(ne))
+        rp, cp, ch = i64(refiPatt, np.full(ne, 7)), i64(child_ptr, np.zeros(ne + 1)), i64(child, np.zeros(0))
+        h = C.c_void_p()
+        _check(lib().ddpca_multigrid_create(len(xyz), _ptr(xyz), ne, _ptr(cn), _ptr(pa), _ptr(lv), _ptr(rp), _ptr(cp),
+                                            _ptr(ch), C.byref(h)))
+        self._h = h
+        self.nnode = len(xyz)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.ddpca_multigrid_destroy(h)
+            self._h = None
+
+    def set(self, what: str, idx=None, val=None) -> "TreeMultigrid":
+        i = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        v = None if val is None else np.ascontiguousarray(val, dtype=np.float64).reshape(-1)
+        n = len(i) if i is not None else len(v)
+        _check(lib().ddpca_multigrid_set(self._h, what.encode(), n, None if i is None else _ptr(i),
+                                         None if v is None else _ptr(v)))
+        return self
+
+    def build(self) -> "TreeMultigrid":
+        _check(lib().ddpca_multigrid_build(self._h, None))
+        return self
+
+    def view(self, what: str, level: int = 0) -> np.ndarray:
+        data, count, dt = C.c_void_p(), C.c_int64(), C.c_int()
+        _check(lib().ddpca_multigrid_view(self._h, what.encode(), level, C.byref(data), C.byref(count), C.byref(dt)))
+        dtype = np.dtype(_DTYPES[dt.value])
+        if count.value == 0:
+            return np.zeros(0, dtype)
+        buf = (C.c_char * (count.value * dtype.itemsize)).from_address(data.value)
+        return np.frombuffer(buf, dtype=dtype).copy()
+
+    @property
+    def posiNode(self) -> np.ndarray:
+        return self.view("posiNode")
+
+    def stress(self, u: np.ndarray, device: int = 0) -> np.ndarray:
+        """MULTIGRID::STRESS_RECOVERY (MULTIGRID.h:1316-1433): u = the nodal displacement in
+        positions (3 N, rotated nodes in their own frame, as OUTP_SUB1 returns it); returns N x 7
+        (xx, yy, zz, xy, yz, zx, von Mises) in positions.  device < 0: the host restatement."""
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(-1)
+        if len(u) != 3 * self.nnode:
+            raise ValueError(f"stress: u needs {3 * self.nnode} entries, got {len(u)}")
+        out = np.zeros((self.nnode, 7))
+        _check(lib().ddpca_multigrid_stress(self._h, device, _ptr(u), _ptr(out)))
+        return out
+
+
 # ============================================================================ device MGPIS
 class MGPIS:
     """Device multigrid-preconditioned CG for one subdomain (MGPIS.h:8-225)."""
@@ -795,6 +867,20 @@ def write_resuMoni(path: str, rows: np.ndarray) -> None:
     _check(lib().ddpca_write_resuMoni(str(path).encode(), _ptr(r), r.shape[0], r.shape[1]))
 
 
+def write_resuStre(path: str, stre: np.ndarray) -> None:
+    """resuStre_<tv>.txt (MULTIGRID.h:1416-1430): one line of seven fields per row of stre (N x 7)."""
+    s = np.ascontiguousarray(stre, dtype=np.float64).reshape(-1, 7)
+    _check(lib().ddpca_write_resuStre(str(path).encode(), _ptr(s), len(s)))
+
+
+def stress_last_kernel_ms() -> tuple:
+    """HIP-event times (ms) of the element and node kernels of this thread's last device stress
+    recovery (ddpca_stress_last_kernel_ms; measurement only)."""
+    out = (C.c_double * 2)()
+    _check(lib().ddpca_stress_last_kernel_ms(out))
+    return out[0], out[1]
+
+
 def mass_solve(systems: Sequence, b: np.ndarray, rtol: float = 1e-14, maxit: int = 2000, fuse_alpha: int = -1,
                device: int = 0):
     """The ADMM loop's batched surface-mass Jacobi-PCG on its own (ddpca_mass_solve): systems = square
@@ -887,6 +973,18 @@ class MCONTACT:
             _check(lib().mcontact_gpu_get(self._h, what.encode(), index, _ptr(out), n))
         return out
 
+    def stress(self, tv: int) -> np.ndarray:
+        """Nodal stresses of the owned subdomain tv from its device-resident resuDisp
+        (mcontact_gpu_stress; MULTIGRID::STRESS_RECOVERY, MULTIGRID.h:1316-1433): N x 7."""
+        n = _check(lib().mcontact_gpu_stress(self._h, self.problem.handle, tv, None, 0))
+        out = np.zeros(n)
+        _check(lib().mcontact_gpu_stress(self._h, self.problem.handle, tv, _ptr(out), n))
+        return out.reshape(-1, 7)
+
+    def STRESS_RECOVERY(self, tv: int, path: str) -> None:
+        """resuStre_<tv>.txt of an owned subdomain (MULTIGRID.h:1316-1433)."""
+        write_resuStre(path, self.stress(tv))
+
     # ---- result files in the reference's formats (host writers, include/ddpca_amd.h)
     def OUTP_SUB2(self, tv: int, path: str) -> None:
         """resuDisp_<tv>.txt of an owned subdomain (MULTIGRID::OUTP_SUB2, MULTIGRID.h:1288-1307)."""
@@ -921,7 +1019,7 @@ class MCONTACT:
         return d
 
 
-__all__ = ["Problem", "MULTIGRID", "MGPIS", "MCONTACT", "DdpcaError", "lib", "gpu_available", "default_options",
+__all__ = ["Problem", "MULTIGRID", "TreeMultigrid", "write_resuStre", "MGPIS", "MCONTACT", "DdpcaError", "lib", "gpu_available", "default_options",
            "contact_search", "mass_solve", "stream_ceiling", "probe_grid_barrier",
            "LIBPATH", "HEADLINE_OPTIONS", "HEADLINE_OPTIONS_SMALL", "headline_options", "HEADLINE_MUSC",
            "HEADLINE_WORKLOAD",

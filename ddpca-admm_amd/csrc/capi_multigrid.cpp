@@ -61,6 +61,15 @@ ddpca_multigrid& open(ddpca_multigrid_t h, bool want_built) {
 
 }  // namespace
 
+// the handle's MULTIGRID for the stress entries (capi_stress.hip); null for a null handle
+namespace ddpca {
+MULTIGRID* multigrid_of(ddpca_multigrid_t h, bool* built) {
+    if (!h) return nullptr;
+    *built = h->built;
+    return &h->g;
+}
+}  // namespace ddpca
+
 // CURVEDS (CURVEDS.h:8-121): a curved surface as a grid of points indiPoin[i][j] with the reverse
 // map point -> (i, j) under the mesh's coordinate comparison.  REFINE_SEARCH: a corner set lies on
 // the surface when every corner is a grid point; its new node is the point at the corners'
@@ -441,6 +450,14 @@ int ddpca_multigrid_view(ddpca_multigrid_t h, const char* what, int64_t level, c
             lev(0, L - 1);
             M.csr = g.realProl(level);
             csr_part(w.substr(2));
+        } else if (w.rfind("stress:", 0) == 0) {  // the stress recovery's plan (MULTIGRID::STRESS_PLAN)
+            const StressPlan& S = M.g.STRESS_PLAN();
+            const std::string part = w.substr(7);
+            if (part == "ptr") put(S.ptr, data, count, dtype);
+            else if (part == "leaf") put(S.leaf, data, count, dtype);
+            else if (part == "mask") put(S.mask, data, count, dtype);
+            else if (part == "corner") put(S.corner, data, count, dtype);
+            else throw ApiError(DDPCA_EINVAL, "stress plan part must be ptr, leaf, mask or corner");
         } else if (w.rfind("H:", 0) == 0) {  // prolOper[maxiLeve]'s rows past the fine level
             M.csr = g.hangRows();
             csr_part(w.substr(2));

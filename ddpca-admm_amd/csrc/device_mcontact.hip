@@ -45,6 +45,7 @@
 
 #include "../../include/ddpca_amd.h"
 #include "device_mgpis.hpp"
+#include "device_stress.hpp"
 #include "problem.hpp"
 
 using namespace ddpca;
@@ -3123,6 +3124,24 @@ bool iterate_once(ddpca_mcontact& H, bool check) {
 }
 
 }  // namespace
+
+// resuDisp of an owned subdomain where it lives in the workspace (mcontact_gpu_stress,
+// capi_stress.hip): the fine level's dofs, then the hanging level's (mcontact_gpu_get "resuDisp")
+namespace ddpca {
+bool mcontact_sub_disp(mcontact_t h, int64_t tv, SubDisp* out) {
+    for (const auto& S : h->subs)
+        if (S.tv == tv) {
+            out->device = h->device;
+            out->stream = h->main;
+            out->u_main = h->u + S.dof0;
+            out->u_hang = h->u + h->oH + S.hoff;
+            out->nn = S.nn;
+            out->nh = S.nh;
+            return true;
+        }
+    return false;
+}
+}  // namespace ddpca
 
 extern "C" {
 

@@ -367,6 +367,8 @@ void MULTIGRID::REFINE(std::set<int64_t>& split, const std::map<int64_t, std::se
 // ---------------------------------------------------------------------------------- transfer
 void MULTIGRID::TRANSFER() {
     const int64_t N = numNodes();
+    strePlan.reset();
+    hangMap.clear();
     // uniform refinement of a generator (REFINE_ALL, no coupling): node ids are already the
     // reference's positions and every new node's parents are recorded -- the fast path below is
     // the general algorithm's result on such a tree (tests/test_host_operators.py checks that)
@@ -618,6 +620,12 @@ void MULTIGRID::TRANSFER_GENERAL() {
     lattNode.clear();
     for (auto& e : elemVect)
         for (auto& c : e.cornNode) c = pos[c];
+    for (const auto& kv : ininTran[L]) {
+        std::vector<int64_t> key;
+        for (int64_t p : kv.first) key.push_back(pos[p]);
+        std::sort(key.begin(), key.end());
+        hangMap.emplace_back(std::move(key), pos[kv.second]);
+    }
     general = true;
 }
 

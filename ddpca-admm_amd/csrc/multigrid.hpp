@@ -18,15 +18,18 @@
 //                                              step, the hierarchy, Dirichlet condensation
 //   ADDITIONAL_FORCE     MULTIGRID.h:1257-1261
 //   OUTP_SUB1            MULTIGRID.h:1263-1281
+//   STRESS_RECOVERY      MULTIGRID.h:1316-1433 nodal stresses + von Mises (stress.cpp; the device
+//                                              kernels read the same plan, device_stress.hip)
 // A general tree comes in through the C ABI (ddpca_multigrid_*, capi_multigrid.cpp) with the
 // element tree the caller built or refined (ddpca_multigrid_refine); TRANSFER then renumbers the
 // nodes to the reference's positions (posiNode keeps the original ids: earlTran).  Out of scope
 // here: the curved-surface projection itself (CURVEDS: the caller supplies its
-// planSurf), stress recovery, text output.
+// planSurf), text output.
 #pragma once
 #include <array>
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <set>
 #include <unordered_map>
 #include <vector>
@@ -44,6 +47,20 @@ struct TreeElem {
                               // 4 xi, 5 eta, 6 zeta (the pattern the element WAS refined with), 7 leaf
     std::vector<int64_t> children;  // general trees (capi_multigrid.cpp); REFINE_ALL fills it too
     bool leaf() const { return firstChild < 0 && children.empty(); }
+};
+
+// What STRESS_RECOVERY needs besides the displacement (STRESS_PLAN): the leaf elements' corners
+// and, per node, its contributions in the reference's order.  Every contribution is the mean of a
+// subset of one leaf element's 8 nodal-stress rows, so it is stored as (leaf index, corner mask).
+struct StressPlan {
+    int64_t nnode = 0, nleaf = 0;
+    std::vector<int32_t> corner;    // 8 nleaf: corner positions of leaf element l (elemVect order)
+    std::vector<int64_t> ptr;       // nnode + 1: contributions of node p are [ptr[p], ptr[p + 1])
+    std::vector<int32_t> leaf;      // contribution -> leaf index
+    std::vector<uint8_t> mask;      // contribution -> corners whose rows are averaged
+    std::vector<int32_t> rotIndex;  // nnode: index into rot of a nodeRota node, else -1
+    std::vector<double> rot;        // 9 per rotated node, row-major
+    std::shared_ptr<void> device;   // the device copy (device_stress.hip), made on first use
 };
 
 class MULTIGRID {
@@ -97,6 +114,9 @@ public:
     bool general = false;
     std::vector<int64_t> posiNode;
     Stencil hangStencil;
+    // PATCH's map of the hanging level (the reference's conoFino; finoCono is its reverse): sorted
+    // parent corner set -> hanging node, both in positions, in the map's order
+    std::vector<std::pair<std::vector<int64_t>, int64_t>> hangMap;
     // the reference's algorithm on any tree (forced on uniform trees too with force_general, tests)
     void TRANSFER_GENERAL();
     bool force_general = false;
@@ -142,6 +162,16 @@ public:
     void ADDITIONAL_FORCE(const double* f_nodal, double* f_free) const;
     // u_nodal = earlTran * prolOper * [x_free scattered; prescribed values]
     void OUTP_SUB1(const double* x_free, double* u_nodal) const;
+
+    // ---------------------------------------------------------------- stress recovery
+    // MULTIGRID::STRESS_RECOVERY (MULTIGRID.h:1316-1433) on the tree after TRANSFER / PATCH, in the
+    // nodal vectors' numbering (positions on general trees).  u_nodal: 3 nodalCount() values as
+    // OUTP_SUB1 returns them (rotated nodes in their own frame); stre7: 7 per node, the six Voigt
+    // components xx, yy, zz, xy, yz, zx and the von Mises stress.  A node with no contribution
+    // gets 0 / 0 = NaN, as in the reference.  STRESS_PLAN builds the plan once and keeps it.
+    std::shared_ptr<StressPlan> strePlan;
+    const StressPlan& STRESS_PLAN();
+    void STRESS_RECOVERY(const double* u_nodal, double* stre7);
 
     // reference-layout operators (MGPIS::consStif / realProl, condensed scalar CSR)
     Csr consStif(int64_t level) const;

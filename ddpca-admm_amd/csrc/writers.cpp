@@ -90,4 +90,17 @@ int ddpca_write_resuMoni(const char* path, const double* rows, int64_t nrows, in
     });
 }
 
+// resuStre_<tv>.txt (MULTIGRID::STRESS_RECOVERY, MULTIGRID.h:1416-1430): six stress components
+// and the von Mises stress per node
+int ddpca_write_resuStre(const char* path, const double* stre, int64_t nnodes) {
+    return guarded([&] {
+        if (nnodes < 0 || (nnodes > 0 && !stre)) throw ApiError(DDPCA_EINVAL, "ddpca_write_resuStre: bad arguments");
+        File out(path);
+        for (int64_t i = 0; i < nnodes; ++i) {
+            for (int c = 0; c < 7; ++c) out.num(stre[7 * i + c]);
+            out.end();
+        }
+    });
+}
+
 }  // extern "C"

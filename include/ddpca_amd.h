@@ -325,7 +325,11 @@ int ddpca_problem_set_hanging(ddpca_problem_t p, int64_t tv, int64_t nnodes_all,
  *     cumulative positions per level 0..maxiLeve, then the total incl. the hanging level),
  *     "freeCount", "consFlag" (uint8 per position dof), "consForc", "dispForc", and CSR parts
  *     ("<X>:ptr|col|val|shape") of "K" (MGPIS::consStif[level]), "P" (MGPIS::realProl[level],
- *     level+1 <- level) and "H" (rows 3 NL.. of prolOper[maxiLeve], positions: the hanging level).
+ *     level+1 <- level) and "H" (rows 3 NL.. of prolOper[maxiLeve], positions: the hanging level);
+ *     the stress recovery's plan: "stress:corner" (int32, 8 positions per leaf element),
+ *     "stress:ptr" (positions + 1), "stress:leaf" (int32) and "stress:mask" (uint8): node p's
+ *     contributions [ptr[p], ptr[p+1]) in the reference's order, each the mean of the rows of leaf
+ *     element leaf[q]'s nodal stresses that mask[q] selects.
  *   set_subdomain_multigrid: subdomain tv of an operator-level problem from the built tree (what
  *     set_subdomain(_prol) + set_hanging take from the reference's own MULTIGRID); interface
  *     operators handed over afterwards are in the position numbering (posiNode maps them). */
@@ -367,6 +371,15 @@ int ddpca_multigrid_build(ddpca_multigrid_t g, const ddpca_csr_t* extra);
 int ddpca_multigrid_view(ddpca_multigrid_t g, const char* what, int64_t level, const void** data, int64_t* count,
                          int* dtype);
 int ddpca_problem_set_subdomain_multigrid(ddpca_problem_t p, int64_t tv, ddpca_multigrid_t g);
+/* MULTIGRID::STRESS_RECOVERY (MULTIGRID.h:1316-1433) on the built tree (after
+ * ddpca_multigrid_build): nodal stresses from a nodal displacement.  disp has 3 nodalCount entries
+ * in the numbering and frame OUTP_SUB1 returns (positions; a nodeRota node in its rotated frame:
+ * what mcontact_gpu_get "resuDisp" gives); stre gets 7 per node: the Voigt components xx, yy, zz,
+ * xy, yz, zx of the L2-projected, node-averaged stress and the von Mises stress.  A node no leaf
+ * element contributes to gets NaN (the reference's 0 / 0).  device >= 0: the fp64 kernels on that
+ * GPU (the plan is uploaded on the first call and kept with g); device < 0: the host restatement
+ * (OpenMP).  DDPCA_EINVAL for a NULL argument or a multigrid that is not built. */
+int ddpca_multigrid_stress(ddpca_multigrid_t g, int device, const double* disp, double* stre);
 /* The whole MCONTACT::ESTABLISH (MCONTACT.h:181-896) from element trees: subdomain tv of an empty
  * problem (ddpca_problem_empty) takes a copy of the UNBUILT multigrid g (its tree and the inputs
  * set with ddpca_multigrid_set: constraints, loads, rotations, coupled nodes, material);
@@ -489,6 +502,17 @@ int mcontact_gpu_timing(mcontact_t h, double* out10);
  * snapshots and norms, [7] body-balance PCG kernel launches (not bytes).  Returns the count (8);
  * copies min(8, cap) when out != NULL.  No equivalent in the reference (measurement only). */
 int64_t mcontact_gpu_bytes(mcontact_t h, double* out, int64_t cap);
+/* MULTIGRID::STRESS_RECOVERY (MULTIGRID.h:1316-1433) from the device-resident resuDisp of the
+ * owned subdomain tv, with no host round trip of the displacement: the kernels and the plan of
+ * ddpca_multigrid_stress on the subdomain's mesh, which p supplies (the problem h was created
+ * from, as in mcontact_gpu_comm_loopback).  Returns 7 N (N = the subdomain's nodal count) and
+ * copies min(7 N, cap) doubles when out != NULL.  DDPCA_EINVAL when tv is not owned by this rank
+ * or the subdomain has no element tree (operator-level problems, ddpca_problem_set_subdomain). */
+int64_t mcontact_gpu_stress(mcontact_t h, ddpca_problem_t p, int64_t tv, double* out, int64_t cap);
+/* Measurement only (profiles/stress_probe.py; no reference counterpart): HIP-event times in ms of
+ * the two kernels of the calling thread's last device stress recovery (ddpca_multigrid_stress
+ * with device >= 0, mcontact_gpu_stress): out2[0] the element kernel, out2[1] the node kernel. */
+int ddpca_stress_last_kernel_ms(double* out2);
 int mcontact_gpu_destroy(mcontact_t h);
 /* The batched surface-mass solver of the ADMM loop on its own (replaces the interface mass solves
  * of MCONTACT.h:2671-2704: SimplicialLDLT below 120000 rows, MCONTACT.h:838-847, Eigen CG above,
@@ -571,6 +595,11 @@ int ddpca_write_resuCont(const char* path, double fric, int64_t nip, const doubl
                          const int32_t* stat, const double* basis);
 /* resuMoni.txt (MCONTACT.h:2502, 2742-2836): the rows of mcontact_gpu_monitor. */
 int ddpca_write_resuMoni(const char* path, const double* rows, int64_t nrows, int64_t ncols);
+/* resuStre_<tv>.txt (MULTIGRID::STRESS_RECOVERY's output, MULTIGRID.h:1316-1433, layout
+ * 1416-1430): one line of seven fields per node, stre[7*nnodes] as ddpca_multigrid_stress /
+ * mcontact_gpu_stress return it (rows in the order the caller wants them: node ids through
+ * posiNode on general trees). */
+int ddpca_write_resuStre(const char* path, const double* stre, int64_t nnodes);
 
 #ifdef __cplusplus
 }
