@@ -191,6 +191,8 @@ def _declare(L: C.CDLL) -> None:
     L.ddpca_stress_last_kernel_ms.argtypes = [_DP]
     L.mgpis_gpu_vcycle.argtypes = [_P, _P, _P]
     L.mgpis_gpu_info.argtypes = [_P, _I64P]
+    L.mgpis_gpu_vcycle_info.argtypes = [_P, C.c_char_p, C.c_int, _P, C.c_int64]
+    L.mgpis_gpu_vcycle_info.restype = C.c_int64
     L.mgpis_gpu_bench_spmv.argtypes = [_P, C.c_int, C.c_int, _DP, _DP]
     L.mgpis_gpu_destroy.argtypes = [_P]
     if hasattr(L, "mcontact_gpu_create"):
@@ -780,6 +782,23 @@ class MGPIS:
         _check(lib().mgpis_gpu_info(self._h, out))
         return dict(nlev=out[0], nfree=out[1], nnzb=out[2], chunks=out[3], omega=out[4] / 1e6, lmax=out[5] / 1e6,
                     device=out[6])
+
+    def vcycle_info(self, what: str, level: Optional[int] = None) -> np.ndarray:
+        """Read-only diagnostic of the V-cycle's setup (mgpis_gpu_vcycle_info): "lmax" (doubles, one per
+        member) and "coef" (doubles, (c1, c2) per sweep and member) of a level >= 1 (default: the fine
+        one), "colour" (int32 per fine node in the reference numbering, -1 = not colour-swept),
+        "levels" (int32, nlev x [exact level, lattice transfers, rotation block entries, fp32 iterate
+        copy, V-cycle copy's storage type])."""
+        lev = self.info()["nlev"] - 1 if level is None else int(level)
+        n = lib().mgpis_gpu_vcycle_info(self._h, what.encode(), lev, None, 0)
+        if n < 0:
+            _check(int(n))
+        out = np.zeros(n, dtype=np.float64 if what in ("lmax", "coef") else np.int32)
+        if n:
+            m = lib().mgpis_gpu_vcycle_info(self._h, what.encode(), lev, _ptr(out), n)
+            if m < 0:
+                _check(int(m))
+        return out.reshape(-1, 5) if what == "levels" else out
 
     def bench_spmv(self, variant: int = 0, reps: int = 20) -> tuple:
         """Diagnostic: (ms per launch, algorithmic bytes per launch) of a fine-level kernel variant."""

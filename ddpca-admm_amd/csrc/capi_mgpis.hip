@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <string>
+#include <vector>
 
 #include "../../include/ddpca_amd.h"
 #include "device_mgpis.hpp"
@@ -163,7 +165,9 @@ int ddpca_problem_mgpis(ddpca_problem_t p, int64_t tv, int device, const mgpis_o
         std::vector<const Bsr3*> Bp;
         std::vector<const Stencil*> Sp;
         for (const auto& b : g.levelStif) Bp.push_back(&b);
-        for (const auto& s : g.scalProl) Sp.push_back(&s);
+        // prolOper: scalProl with the nodal rotations' 3x3 blocks as block entries (== scalProl without
+        // nodeRota), as the MCONTACT batch takes it; an operator-level subdomain has scalProl only
+        for (const auto& s : g.prolOper.empty() ? g.scalProl : g.prolOper) Sp.push_back(&s);
         auto h = std::make_unique<ddpca_mgpis>();
         h->dev = single(device, nn, Bp, g.consFlag, Sp, opt, g.nodeCoor.empty() ? nullptr : g.nodeCoor[0].data());
         *out = h.release();
@@ -294,6 +298,59 @@ int mgpis_gpu_info(mgpis_t h, int64_t* out7) {
         out7[5] = (int64_t)(lmax * 1e6);
         out7[6] = D.device;
     });
+}
+
+int64_t mgpis_gpu_vcycle_info(mgpis_t h, const char* what, int level, void* out, int64_t cap) {
+    int64_t count = 0;
+    const int rc = guarded([&] {
+        if (!h || !what) throw ApiError(DDPCA_EINVAL, "null argument");
+        MgpisDevice& D = *h->dev;
+        select_device(D.device);
+        const int nlev = (int)D.lev.size();
+        const std::string w(what);
+        // copy v out (out == NULL: the size query)
+        auto put = [&](const auto& v) {
+            count = (int64_t)v.size();
+            if (!out) return;
+            if (cap < count) throw ApiError(DDPCA_EINVAL, "vcycle_info: out is too small");
+            if (count) std::memcpy(out, v.data(), v.size() * sizeof(v[0]));
+        };
+        if (w == "lmax" || w == "coef") {
+            // (level 0 is never smoothed: no spectrum estimate, no coefficient table)
+            if (level < 1 || level >= nlev) throw ApiError(DDPCA_EINVAL, "vcycle_info: level");
+            if (w == "lmax") put(D.lev[level].lmax);
+            else put(D.lev[level].coef.download());
+        } else if (w == "colour") {
+            // the colour of a node = the group of the colour chunk that sweeps it (GsFine::list,
+            // rowidx: what the sweeps run over), mapped back through the device numbering
+            const LevelDev& F = D.lev.back();
+            std::vector<int32_t> dev(F.nn, -1);
+            if (D.gs_fine()) {
+                const std::vector<int32_t> list = D.gs.list.download(), rowidx = D.gs.rowidx.download();
+                for (int k = 0; k < D.gs.ncol; ++k)
+                    for (int64_t q = D.gs.first[k]; q < D.gs.first[k] + D.gs.count[k]; ++q)
+                        for (int64_t lane = 0; lane < kChunk; ++lane) {
+                            const int32_t rr = rowidx[(int64_t)list[q] * kChunk + lane];
+                            if (rr >= 0) dev[rr] = k;
+                        }
+            }
+            std::vector<int32_t> ref;
+            for (int s = 0; s < D.nsub; ++s)
+                for (int64_t i = 0; i < F.nloc[s]; ++i) ref.push_back(dev[F.noff[s] + D.fine_perm[s][i]]);
+            put(ref);
+        } else if (w == "levels") {
+            std::vector<int32_t> v;
+            for (int l = 0; l < nlev; ++l) {
+                const LevelDev& L = D.lev[l];
+                const bool x4 = (l == nlev - 1 && D.gs_fine()) ? D.gs.x4.p != nullptr : L.x4a.p != nullptr;
+                for (int e : {D.clev, (int)L.lat, (int)(L.nrot != 0), (int)x4, D.vc_type(l)}) v.push_back(e);
+            }
+            put(v);
+        } else {
+            throw ApiError(DDPCA_EINVAL, "vcycle_info: unknown item");
+        }
+    });
+    return rc != 0 ? rc : count;
 }
 
 int mgpis_gpu_bench_spmv(mgpis_t h, int variant, int reps, double* ms, double* bytes) {

@@ -169,6 +169,23 @@ int mgpis_gpu_spmv_copy(mgpis_t h, int level, int vcycle_copy, const double* x, 
 int mgpis_gpu_vcycle(mgpis_t h, const double* r, double* z);
 /* Informational: [nlev, n_fine_free, nnzb_fine, chunks_fine, omega*1e6, lambda_max*1e6, device] */
 int mgpis_gpu_info(mgpis_t h, int64_t* out7);
+/* Read-only diagnostic of the V-cycle's setup decisions (no reference counterpart), for parity tests
+ * of the V-cycle against a host restatement (tests/vcycle_host.py): copies data the create left,
+ * launches no kernel.  Returns the element count, or a negative DDPCA_E* code (unknown `what`, a
+ * level without the item, cap < count); out == NULL queries the count.
+ *   "lmax"    double per member: the level's lambda_max(M K) estimate with its 1.05 margin
+ *             (24 power iterations at create); levels >= 1
+ *   "coef"    double: the level's smoother coefficient table as the sweeps read it,
+ *             [(sweep * members + member) * 2 + {0, 1}] = (c1, c2), sweeps 0..nu; levels >= 1
+ *   "colour"  int32 per fine-level node, in the caller's (reference) node numbering, member after
+ *             member: the node's colour under smoothers 3 / 4, -1 for a node outside the band or
+ *             when the fine level is not colour-swept (level is ignored)
+ *   "levels"  int32, five per level: the exact level of the coarse solve (the same on every level), 1
+ *             when the lattice transfer form was accepted into this level, 1 when the transfer into
+ *             it carries rotation block entries, 1 when its iterate lives in an fp32 copy, the storage
+ *             type of its V-cycle copy (0 fp64, 1 fp32, 2 block-exponent fp16, 3 block-scaled int8)
+ *             (level is ignored) */
+int64_t mgpis_gpu_vcycle_info(mgpis_t h, const char* what, int level, void* out, int64_t cap);
 /* Diagnostic (no reference counterpart): average ms per launch of a fine-level SELL-BSR3
  * kernel over `reps` back-to-back launches on this operator.  variant = loop (0 cached x3
  * unroll, 1 non-temporal matrix loads, 2 column prefetch + non-temporal, 3 a bound only: x

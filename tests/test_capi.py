@@ -61,6 +61,7 @@ def test_round5_entry_points_refuse_bad_arguments(ddpca):
     L = ddpca.lib()
     assert L.mcontact_gpu_comm_loopback(None, None) == -1
     assert L.mgpis_gpu_spmv_copy(None, 0, 1, None, None) == -1
+    assert L.mgpis_gpu_vcycle_info(None, b"lmax", 1, None, 0) == -1  # (the V-cycle setup diagnostic)
     assert L.ddpca_problem_set_contact(None, 0, 0, 1) == -1
     assert L.ddpca_problem_set_subdomain_tree(None, 0, None) == -1
     h = ctypes.c_void_p()

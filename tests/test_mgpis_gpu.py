@@ -9,6 +9,7 @@ import scipy.sparse as sp
 import pytest
 
 from conftest import CASE_PARAMS, golden
+from vcycle_host import round_blocks as _round_blocks
 
 pytestmark = pytest.mark.gpu
 
@@ -261,25 +262,6 @@ def test_int8_smoother_copy_keeps_the_solution(ddpca, gpu):
         assert rr <= 1e-14
         assert i3 <= i2 + 2, (i3, i2)
         assert np.linalg.norm(x3 - x2) <= 1e-10 * np.linalg.norm(x2)
-
-
-def _round_blocks(K, node, kind):
-    """K with every 3x3 node block rounded as the device stores its V-cycle copy: kind 2 block-exponent
-    fp16 (2^e x fp16, e = frexp exponent of the block maximum), kind 3 block-scaled int8 (scale =
-    the block maximum / 127 in fp32 with its low 8 bits cleared, values rounded and clamped to +-127)"""
-    Kc = K.tocoo()
-    key = node[Kc.row].astype(np.int64) * (node.max() + 1) + node[Kc.col]
-    _, inv = np.unique(key, return_inverse=True)
-    mx = np.zeros(inv.max() + 1)
-    np.maximum.at(mx, inv, np.abs(Kc.data))
-    if kind == 2:
-        e = np.frexp(mx)[1][inv]
-        v = np.ldexp(np.ldexp(Kc.data, -e).astype(np.float16).astype(np.float64), e)
-    else:
-        s32 = (mx / 127.0).astype(np.float32).view(np.uint32) & np.uint32(0xFFFFFF00)
-        sc = s32.view(np.float32).astype(np.float64)[inv]
-        v = np.clip(np.rint(Kc.data / sc), -127, 127) * sc
-    return sp.csr_matrix((v, (Kc.row, Kc.col)), shape=K.shape)
 
 
 @pytest.mark.parametrize("lowp", [2, 3])
