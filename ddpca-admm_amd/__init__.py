@@ -180,6 +180,7 @@ def _declare(L: C.CDLL) -> None:
     L.ddpca_write_resuCont.argtypes = [C.c_char_p, C.c_double, C.c_int64, _P, _P, _P]
     L.ddpca_write_resuMoni.argtypes = [C.c_char_p, _P, C.c_int64, C.c_int64]
     L.ddpca_write_resuStre.argtypes = [C.c_char_p, _P, C.c_int64]
+    L.ddpca_write_resuFreq.argtypes = [C.c_char_p, _P, _P, C.c_int64]
     L.ddpca_multigrid_create.argtypes = [C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.POINTER(_P)]
     L.ddpca_multigrid_set.argtypes = [_P, C.c_char_p, C.c_int64, _P, _P]
     L.ddpca_multigrid_build.argtypes = [_P, _P]
@@ -213,6 +214,10 @@ def _declare(L: C.CDLL) -> None:
         L.mcontact_gpu_bytes.restype = C.c_int64
         L.mcontact_gpu_destroy.argtypes = [_P]
         L.mcontact_gpu_comm_check.argtypes = [_P, C.c_int64]
+        L.mcontact_gpu_apps.argtypes = [_P, C.c_int64, C.c_int64, C.c_double, C.c_int64, _P, _P, _P, _P]
+        L.mcontact_gpu_apps_mode.argtypes = [_P, C.c_int64, C.c_int64, _P, C.c_int64]
+        L.mcontact_gpu_apps_mode.restype = C.c_int64
+        L.ddpca_eigs_orth_bench.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int, _DP]
         L.ddpca_mass_solve.argtypes = [C.c_int, C.c_int64, C.POINTER(_CsrArg), _P, _P, C.c_double, C.c_int64, C.c_int,
                                        _P]
 
@@ -892,6 +897,15 @@ def write_resuStre(path: str, stre: np.ndarray) -> None:
     _check(lib().ddpca_write_resuStre(str(path).encode(), _ptr(s), len(s)))
 
 
+def write_resuFreq(path: str, freq: np.ndarray, corr: np.ndarray) -> None:
+    """resuFreq.txt (MCONTACT::APPS, MCONTACT.h:2368-2377): one line "eigenvalue correlation" per mode."""
+    f = np.ascontiguousarray(freq, dtype=np.float64).reshape(-1)
+    c = np.ascontiguousarray(corr, dtype=np.float64).reshape(-1)
+    if len(f) != len(c):
+        raise ValueError("write_resuFreq: freq and corr differ in length")
+    _check(lib().ddpca_write_resuFreq(str(path).encode(), _ptr(f), _ptr(c), len(f)))
+
+
 def stress_last_kernel_ms() -> tuple:
     """HIP-event times (ms) of the element and node kernels of this thread's last device stress
     recovery (ddpca_stress_last_kernel_ms; measurement only)."""
@@ -1004,6 +1018,40 @@ class MCONTACT:
         """resuStre_<tv>.txt of an owned subdomain (MULTIGRID.h:1316-1433)."""
         write_resuStre(path, self.stress(tv))
 
+    def APPS(self, nev: int = 10, tol: float = 1e-6, ncv: Optional[int] = None, max_restarts: int = 100,
+             directory=None) -> dict:
+        """MCONTACT::APPS (MCONTACT.h:2343-2403; SOLVE(appsCont = 0)): the nev eigenpairs of smallest
+        magnitude of globCoup_1 (mcontact_gpu_apps) and their correlation with globForc_1.  Returns
+        freq (ascending), corr (>= 0), resid (true relative residuals), steps, restarts, solves.
+        With directory: resuFreq.txt and resuDisp_<k+1>-<tv>.txt for every mode and owned subdomain.
+        Not converged after max_restarts: DdpcaError(DDPCA_ENOCONV), the best pairs in its .result."""
+        nev = int(nev)
+        m = max(nev, 0)
+        freq, corr, resid = np.zeros(m), np.zeros(m), np.zeros(m)
+        info = np.zeros(4, np.int64)
+        rc = lib().mcontact_gpu_apps(self._h, nev, 0 if ncv is None else int(ncv), float(tol), int(max_restarts),
+                                     _ptr(freq), _ptr(corr), _ptr(resid), _ptr(info))
+        res = dict(freq=freq, corr=corr, resid=resid, steps=int(info[0]), restarts=int(info[1]), solves=int(info[2]))
+        if rc < 0:
+            e = DdpcaError(rc, lib().ddpca_last_error().decode())
+            e.result = res
+            raise e
+        if directory is not None:
+            d = os.fspath(directory)
+            write_resuFreq(os.path.join(d, "resuFreq.txt"), freq, corr)
+            for k in range(nev):
+                for tv in self.get("owned"):
+                    write_resuDisp(os.path.join(d, f"resuDisp_{k + 1}-{int(tv)}.txt"), self.apps_mode(k, int(tv)))
+        return res
+
+    def apps_mode(self, k: int, tv: int) -> np.ndarray:
+        """Mode shape k of the last APPS on the owned subdomain tv (mcontact_gpu_apps_mode;
+        MCONTACT.h:2384-2393), in the layout of get("resuDisp", tv)."""
+        n = _check(lib().mcontact_gpu_apps_mode(self._h, k, tv, None, 0))
+        out = np.zeros(n)
+        _check(lib().mcontact_gpu_apps_mode(self._h, k, tv, _ptr(out), n))
+        return out
+
     # ---- result files in the reference's formats (host writers, include/ddpca_amd.h)
     def OUTP_SUB2(self, tv: int, path: str) -> None:
         """resuDisp_<tv>.txt of an owned subdomain (MULTIGRID::OUTP_SUB2, MULTIGRID.h:1288-1307)."""
@@ -1038,7 +1086,7 @@ class MCONTACT:
         return d
 
 
-__all__ = ["Problem", "MULTIGRID", "TreeMultigrid", "write_resuStre", "MGPIS", "MCONTACT", "DdpcaError", "lib", "gpu_available", "default_options",
+__all__ = ["Problem", "MULTIGRID", "TreeMultigrid", "write_resuStre", "write_resuFreq", "MGPIS", "MCONTACT", "DdpcaError", "lib", "gpu_available", "default_options",
            "contact_search", "mass_solve", "stream_ceiling", "probe_grid_barrier",
            "LIBPATH", "HEADLINE_OPTIONS", "HEADLINE_OPTIONS_SMALL", "headline_options", "HEADLINE_MUSC",
            "HEADLINE_WORKLOAD",

@@ -416,4 +416,30 @@ int64_t krylov_gmres(MgpisDevice& D, int prec, const double* b, double* x, doubl
     return it;
 }
 
+// One classical Gram-Schmidt pass of w against V[:, :m] composed from the kernels above, as GMRES
+// runs it (device_eigs.hpp; the measurement baseline of device_eigs.hip's fused kernels): the
+// dots kMaxDots columns per launch with the coefficients fetched to the host, then w -= V c with
+// kMaxBasis coefficients per launch as kernel arguments.
+void krylov_cgs_pass(hipStream_t st, int64_t n, const double* V, int64_t ld, int m, double* w, double* partial, double* cdev,
+                     double* chost) {
+    for (int j0 = 0; j0 < m; j0 += kMaxDots) {
+        DotArgs d{};
+        d.m = std::min(kMaxDots, m - j0);
+        for (int k = 0; k < d.m; ++k) {
+            d.a[k] = V + (int64_t)(j0 + k) * ld;
+            d.b[k] = w;
+        }
+        hipLaunchKernelGGL(k_mdot, dim3(kDotBlocks), dim3(kBlock), 0, st, d, n, partial);
+        hipLaunchKernelGGL(k_mdot_fin, dim3(d.m), dim3(kBlock), 0, st, partial, kDotBlocks, cdev + j0);
+    }
+    DDPCA_HIP(hipMemcpyAsync(chost, cdev, m * sizeof(double), hipMemcpyDeviceToHost, st));
+    DDPCA_HIP(hipStreamSynchronize(st));
+    for (int j0 = 0; j0 < m; j0 += kMaxBasis) {
+        Coef c{};
+        const int mm = std::min(kMaxBasis, m - j0);
+        for (int k = 0; k < mm; ++k) c.c[k] = chost[j0 + k];
+        hipLaunchKernelGGL(k_vcomb, dim3(grid_for(n)), dim3(kBlock), 0, st, n, w, -1.0, V + (int64_t)j0 * ld, ld, mm, c, w);
+    }
+}
+
 }  // namespace ddpca

@@ -44,6 +44,7 @@
 #include <unordered_map>
 
 #include "../../include/ddpca_amd.h"
+#include "device_eigs.hpp"
 #include "device_mgpis.hpp"
 #include "device_stress.hpp"
 #include "problem.hpp"
@@ -782,6 +783,24 @@ __global__ void k_cs_presc(const int32_t* cdof, const double* presc, double* u, 
     if (i < n) u[cdof[i]] += presc[cdof[i]];
 }
 
+// APPS with the DOUBLE_M_1 solve: r = b - A x on the fp64 CSR of globCoup_1 (one wavefront per
+// row), and x += d, the refinement step of the Lanczos operator (mcontact_gpu_apps)
+__global__ __launch_bounds__(256) void k_apps_resid(const int64_t* ptr, const int32_t* col, const double* val, int64_t nrow,
+                                                    const double* x, const double* b, double* r) {
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nrow) return;
+    const int lane = threadIdx.x & 63;
+    double s = 0.0;
+    for (int64_t k = ptr[i] + lane; k < ptr[i + 1]; k += 64) s += val[k] * x[col[k]];
+    s = wsum(s);
+    if (lane == 0) r[i] = b[i] - s;
+}
+
+__global__ void k_apps_add(double* x, const double* d, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] += d[i];
+}
+
 // coarse right-hand side into the coarse MGPIS's fine layout / its solution back to the own rows
 __global__ void k_perm_scatter(const int32_t* perm, const double* g, double* b, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1431,6 +1450,10 @@ struct CoarseDev {
     DevBuf<double> pval;
     std::vector<int64_t> own_rows;  // global coarse rows of this rank, in xc order
     double bytes_iter = 0.0;        // algorithmic bytes of one correction (without DOUBLE_M's PCG)
+    // APPS (MCONTACT.h:2343-2403; single-rank, interface-eliminated spaces): the host's globCoup_1
+    // and globForc_1, uploaded for the call's true residuals and correlations
+    Csr apps_A;
+    std::vector<double> apps_f;
     std::vector<double> dense;      // host, until inverted: this rank's rows of globCoup_1 (n x n, zeros elsewhere)
     // DOUBLE_M_1 (MCONTACT.h:2303-2341; the reference's choice once globCoup_1 has DIRE_MAXI rows,
     // 1857-1865): the coarse problem solved by its own MGPIS-PCG, redundantly on every rank, on a
@@ -1685,6 +1708,15 @@ struct ddpca_mcontact {
     MassBatch mb_wv;
     DevBuf<double> rinv;
     CoarseDev cs;
+    // APPS (mcontact_gpu_apps): the kept Ritz vectors of the last call, n x nev column-major, sign
+    // fixed, on the device (mode shapes on demand) and on the host ("apps_vec")
+    struct Apps {
+        int nev = 0;
+        DevBuf<double> Y;
+        std::vector<double> Yh;
+        double ms[3] = {0.0, 0.0, 0.0};
+        double last_solve[2] = {0.0, 0.0};  // DOUBLE_M_1: PCG iterations and recursive ||r|| / ||b|| of the last application
+    } apps;
     std::vector<double> moni_host;
     hipStream_t main = nullptr;          // == mg->stream
     std::unique_ptr<Transport> comm;     // RCCL (any rank count, 1 included), or the in-process test transport
@@ -2488,6 +2520,10 @@ void build_coarse(ddpca_mcontact& H, Problem& P) {
         for (int64_t r = cs.baseReco[H.subs[i].tv]; r < cs.baseReco[H.subs[i].tv + 1]; ++r)
             f0[slot_of(r, H.subs[i].tv)] = cs.globForc_1[r];
     C.f0.upload(f0);
+    if (!cs.latin && H.nranks == 1) {
+        C.apps_A = cs.globCoup_1;
+        C.apps_f.assign(cs.globForc_1.begin(), cs.globForc_1.end());
+    }
     C.gs.alloc(std::max<int64_t>(C.nslot, 1));
     C.g.alloc(std::max<int64_t>(n, 1));
     C.xc.alloc(std::max<int64_t>(C.nown, 1));
@@ -2813,6 +2849,48 @@ void coarse_invert(ddpca_mcontact& H) {
     C.inverted = true;
 }
 
+// xc = the owned rows of globCoup_1^-1 g, on the stream (the coarse correction's solve and the
+// operator of APPS's Lanczos iteration: the same launches).
+void coarse_solve(ddpca_mcontact& H, const double* g, double* xc) {
+    CoarseDev& C = H.cs;
+    hipStream_t st = H.main;
+    const int64_t n = C.n;
+    if (C.mg) {  // mgpi_1.CG_SOLV(1, globForc, globSolu) (MCONTACT.h:2594), on the coarse solver's stream
+        MgpisDevice& M = *C.cmg;
+        DDPCA_HIP(hipEventRecord(C.ev_in, st));
+        DDPCA_HIP(hipStreamWaitEvent(M.stream, C.ev_in, 0));
+        DDPCA_HIP(hipMemsetAsync(M.bs.p, 0, M.bs.n * sizeof(double), M.stream));
+        hipLaunchKernelGGL(k_perm_scatter, dim3(nb256(n)), dim3(256), 0, M.stream, C.cperm.p, g, M.bs.p, n);
+        M.pcg_solve(1, 1.0e-14, std::vector<int64_t>{n});
+        hipLaunchKernelGGL(k_perm_gather, dim3(nb256(C.nown)), dim3(256), 0, M.stream, C.cperm.p, C.cown.p, M.xs.p, xc,
+                           C.nown);
+        DDPCA_HIP(hipEventRecord(C.ev_out, M.stream));
+        DDPCA_HIP(hipStreamWaitEvent(st, C.ev_out, 0));
+    } else {
+        hipLaunchKernelGGL(k_gemv_wave, dim3(ceil_div(C.nown, 4)), dim3(256), 0, st, C.ainv.p, g, xc, C.nown, n);
+    }
+}
+
+// u += OUTP_SUB1(accuProl xc) on the owned subdomains (MCONTACT.h:2600-2610): u = the ADMM state,
+// or a zeroed scratch of the same layout (APPS's mode shapes, MCONTACT.h:2384-2393)
+void coarse_prolong(ddpca_mcontact& H, const double* xc, double* u) {
+    CoarseDev& C = H.cs;
+    hipStream_t st = H.main;
+    if (C.assembled) {
+        if (C.npr)
+            hipLaunchKernelGGL(k_cs_prolong_csr, dim3(nb256(C.npr)), dim3(256), 0, st, C.pptr.p, C.pcol.p, C.pval.p, C.ptgt.p,
+                               xc, u, C.npr);
+        if (C.ncd) hipLaunchKernelGGL(k_cs_presc, dim3(nb256(C.ncd)), dim3(256), 0, st, C.cdof.p, H.presc.p, u, C.ncd);
+        return;
+    }
+    hipLaunchKernelGGL(k_cs_scatter, dim3(nb256(C.nxn)), dim3(256), 0, st, C.xsrc.p, xc, C.xn.p, C.nxn);
+    hipLaunchKernelGGL(k_cs_prolong, dim3(nb256(C.qnn)), dim3(256), 0, st, C.qcol.p, C.qw.p, C.qnn, C.xn.p, C.flag.p,
+                       H.presc.p, u);
+    if (C.npr)  // the nodes the scalar stencil cannot hold (rotation blocks)
+        hipLaunchKernelGGL(k_cs_prolong_csr, dim3(nb256(C.npr)), dim3(256), 0, st, C.pptr.p, C.pcol.p, C.pval.p, C.ptgt.p,
+                           xc, u, C.npr);
+}
+
 // One coarse-space correction (MCONTACT.h:2578-2612) on the stream, after k_outp wrote u.
 void coarse_correct(ddpca_mcontact& H) {
     CoarseDev& C = H.cs;
@@ -2850,33 +2928,8 @@ void coarse_correct(ddpca_mcontact& H) {
     if (H.comm) H.comm->allreduce_sum(C.gs.p, C.nslot, st);
     hipLaunchKernelGGL(k_slot_sum, dim3(nb256(n)), dim3(256), 0, st, C.sptr.p, C.gs.p, C.g.p, n);
     if (!C.nown) return;
-    if (C.mg) {  // mgpi_1.CG_SOLV(1, globForc, globSolu) (MCONTACT.h:2594), on the coarse solver's stream
-        MgpisDevice& M = *C.cmg;
-        DDPCA_HIP(hipEventRecord(C.ev_in, st));
-        DDPCA_HIP(hipStreamWaitEvent(M.stream, C.ev_in, 0));
-        DDPCA_HIP(hipMemsetAsync(M.bs.p, 0, M.bs.n * sizeof(double), M.stream));
-        hipLaunchKernelGGL(k_perm_scatter, dim3(nb256(n)), dim3(256), 0, M.stream, C.cperm.p, C.g.p, M.bs.p, n);
-        M.pcg_solve(1, 1.0e-14, std::vector<int64_t>{n});
-        hipLaunchKernelGGL(k_perm_gather, dim3(nb256(C.nown)), dim3(256), 0, M.stream, C.cperm.p, C.cown.p, M.xs.p, C.xc.p,
-                           C.nown);
-        DDPCA_HIP(hipEventRecord(C.ev_out, M.stream));
-        DDPCA_HIP(hipStreamWaitEvent(st, C.ev_out, 0));
-    } else {
-        hipLaunchKernelGGL(k_gemv_wave, dim3(ceil_div(C.nown, 4)), dim3(256), 0, st, C.ainv.p, C.g.p, C.xc.p, C.nown, n);
-    }
-    if (C.assembled) {
-        if (C.npr)
-            hipLaunchKernelGGL(k_cs_prolong_csr, dim3(nb256(C.npr)), dim3(256), 0, st, C.pptr.p, C.pcol.p, C.pval.p, C.ptgt.p,
-                               C.xc.p, H.u, C.npr);
-        if (C.ncd) hipLaunchKernelGGL(k_cs_presc, dim3(nb256(C.ncd)), dim3(256), 0, st, C.cdof.p, H.presc.p, H.u, C.ncd);
-        return;
-    }
-    hipLaunchKernelGGL(k_cs_scatter, dim3(nb256(C.nxn)), dim3(256), 0, st, C.xsrc.p, C.xc.p, C.xn.p, C.nxn);
-    hipLaunchKernelGGL(k_cs_prolong, dim3(nb256(C.qnn)), dim3(256), 0, st, C.qcol.p, C.qw.p, C.qnn, C.xn.p, C.flag.p,
-                       H.presc.p, H.u);
-    if (C.npr)  // the nodes the scalar stencil cannot hold (rotation blocks)
-        hipLaunchKernelGGL(k_cs_prolong_csr, dim3(nb256(C.npr)), dim3(256), 0, st, C.pptr.p, C.pcol.p, C.pval.p, C.ptgt.p,
-                           C.xc.p, H.u, C.npr);
+    coarse_solve(H, C.g.p, C.xc.p);
+    coarse_prolong(H, C.xc.p, H.u);
 }
 
 // Reference MONITOR (MCONTACT.h:2725-2845) on the reduced norms; true = converged.
@@ -3447,6 +3500,22 @@ int64_t mcontact_gpu_get(mcontact_t h, const char* what, int64_t index, void* ou
                 for (int64_t i = 0; i < std::min(n, cap); ++i) static_cast<double*>(out)[i] = v[i];
             return;
         }
+        if (w == "apps_vec") {  // coarse eigenvector y_index of the last mcontact_gpu_apps (n doubles, unit norm)
+            if (h->apps.nev < 1) throw ApiError(DDPCA_ESTATE, "no mcontact_gpu_apps result");
+            if (index < 0 || index >= h->apps.nev) throw ApiError(DDPCA_EINVAL, "mode index out of range");
+            n = h->cs.n;
+            if (out) std::memcpy(out, h->apps.Yh.data() + index * n, std::min(n, cap) * sizeof(double));
+            return;
+        }
+        if (w == "apps_timing") {
+            // doubles: ms of the operator applications, the orthogonalisation, the Ritz products
+            // (DDPCA_APPS_TIMING=1, else 0); DOUBLE_M_1's last application: PCG iterations, recursive ||r|| / ||b||
+            const double v[5] = {h->apps.ms[0], h->apps.ms[1], h->apps.ms[2], h->apps.last_solve[0], h->apps.last_solve[1]};
+            n = 5;
+            if (out)
+                for (int64_t i = 0; i < std::min<int64_t>(5, cap); ++i) static_cast<double*>(out)[i] = v[i];
+            return;
+        }
         throw ApiError(DDPCA_EINVAL, "unknown quantity " + w);
     });
     return rc < 0 ? rc : n;
@@ -3467,6 +3536,172 @@ int64_t mcontact_gpu_bytes(mcontact_t h, double* out, int64_t cap) {
     if (out)
         for (int64_t i = 0; i < std::min(n, cap); ++i) out[i] = h->bytes[i];
     return n;
+}
+
+// MCONTACT::APPS (MCONTACT.h:2343-2403): the nev eigenpairs of smallest magnitude of globCoup_1 by
+// thick-restart Lanczos on its device-resident inverse (device_eigs.hip), each mode's correlation
+// with the coarse load.  Touches nothing of the ADMM state: the basis and the Ritz vectors are
+// the call's own, the coarse solve's right-hand side and result are columns of that basis.
+int mcontact_gpu_apps(mcontact_t h, int64_t nev, int64_t ncv, double tol, int64_t max_restarts, double* eigval,
+                      double* corr, double* resid, int64_t* info) {
+    return guarded([&] {
+        if (!h) throw ApiError(DDPCA_EINVAL, "mcontact_gpu_apps: NULL handle");
+        if (h->nranks > 1)
+            throw ApiError(DDPCA_EINVAL, "mcontact_gpu_apps: a rank of a multi-rank run holds only its own rows of "
+                                         "globCoup_1^-1 (the distributed eigen-solver is not implemented)");
+        CoarseDev& C = h->cs;
+        if (!C.on || C.latin)
+            throw ApiError(DDPCA_ESTATE, "mcontact_gpu_apps: no interface-eliminated coarse space (muscSett = 2): globCoup_1 is empty");
+        if (!C.inverted || !h->mg) throw ApiError(DDPCA_ESTATE, "mcontact_gpu_apps: coarse space not factorised");
+        const int64_t n = C.n;
+        if (C.nown != n || C.apps_A.nrow != n || (int64_t)C.apps_f.size() != n)
+            throw ApiError(DDPCA_ESTATE, "mcontact_gpu_apps: the handle does not hold every row of globCoup_1");
+        if (ncv == 0) ncv = std::min<int64_t>(20 * nev, n);  // the reference's ncv (MCONTACT.h:2354)
+        if (tol == 0.0) tol = 1.0e-6;                        // and its tolerance (2358)
+        if (nev < 1 || ncv <= nev || ncv > n)
+            throw ApiError(DDPCA_EINVAL, "mcontact_gpu_apps: need 1 <= nev < ncv <= n (n = " + std::to_string(n) + ")");
+        if (ncv > kEigsMaxNcv)
+            throw ApiError(DDPCA_EINVAL, "mcontact_gpu_apps: ncv above " + std::to_string(kEigsMaxNcv));
+        if (!(tol > 0.0) || max_restarts < 0 || !eigval || !corr || !resid)
+            throw ApiError(DDPCA_EINVAL, "mcontact_gpu_apps: tol, max_restarts or a NULL output");
+        select_device(h->device);
+        hipStream_t st = h->main;
+        DDPCA_HIP(hipStreamSynchronize(st));
+        DevBuf<int64_t> aptr;
+        DevBuf<int32_t> acol;
+        DevBuf<double> aval;
+        aptr.upload(C.apps_A.ptr);
+        acol.upload(C.apps_A.col.empty() ? std::vector<int32_t>{0} : C.apps_A.col);
+        aval.upload(C.apps_A.val.empty() ? std::vector<double>{0.0} : C.apps_A.val);
+        h->apps.nev = 0;
+        h->apps.Y.alloc((size_t)n * nev);
+        // the coarse MGPIS's measurement counters belong to the ADMM iterations
+        double keep_bytes[3] = {0, 0, 0}, keep_ms = 0.0, keep_tb = 0.0;
+        int64_t keep_samples = 0, keep_graphs = 0;
+        if (C.cmg) {
+            std::memcpy(keep_bytes, C.cmg->alg_bytes, sizeof(keep_bytes));
+            keep_ms = C.cmg->timed_kernel_ms, keep_tb = C.cmg->timed_kernel_bytes;
+            keep_samples = C.cmg->timed_kernel_samples, keep_graphs = C.cmg->graphs_launched;
+        }
+        auto restore = [&] {
+            if (!C.cmg) return;
+            std::memcpy(C.cmg->alg_bytes, keep_bytes, sizeof(keep_bytes));
+            C.cmg->timed_kernel_ms = keep_ms, C.cmg->timed_kernel_bytes = keep_tb;
+            C.cmg->timed_kernel_samples = keep_samples, C.cmg->graphs_launched = keep_graphs;
+        };
+        DevBuf<double> rres(C.mg ? n : 0), rcor(C.mg ? n : 0);
+        EigsResult R;
+        const char* tenv = std::getenv("DDPCA_APPS_TIMING");
+        try {
+            // DOUBLE_M_1's PCG stops on its recursive residual; its true residual is amplified by
+            // kappa(A) on the lowest modes (2e-7 measured on beam_dd_m2, kappa = 4.8e6) and is the
+            // floor of the eigen-residual.  One refinement step on the true residual removes it:
+            // y = S b, y += S (b - A y), S the coarse correction's solve both times
+            auto op = [&](const double* x, double* y) {
+                coarse_solve(*h, x, y);
+                if (!C.mg) return;
+                hipLaunchKernelGGL(k_apps_resid, dim3(ceil_div(n, 4)), dim3(256), 0, st, aptr.p, acol.p, aval.p, n, y, x, rres.p);
+                coarse_solve(*h, rres.p, rcor.p);
+                hipLaunchKernelGGL(k_apps_add, dim3(nb256(n)), dim3(256), 0, st, y, rcor.p, n);
+            };
+            eigs_smallest(st, n, op, EigsCsr{aptr.p, acol.p, aval.p}, (int)nev, (int)ncv, tol, max_restarts, tenv && tenv[0] == '1',
+                          h->apps.Y.p, R);
+        } catch (...) {
+            restore();
+            throw;
+        }
+        h->apps.last_solve[0] = h->apps.last_solve[1] = 0.0;
+        if (C.cmg) {
+            const PcgScal& sc = C.cmg->sc_host[0];
+            h->apps.last_solve[0] = (double)sc.iter;
+            h->apps.last_solve[1] = sc.bb > 0.0 ? std::sqrt(sc.rr / sc.bb) : 0.0;
+        }
+        restore();
+        // correlations with the load on the host, in row order; unit norm; the sign rule:
+        // corr >= 0, and where |corr| < 1e-12 the component of largest magnitude is positive
+        std::vector<double>& Y = h->apps.Yh;
+        Y = h->apps.Y.download();
+        double fn = 0.0;
+        for (double v : C.apps_f) fn += v * v;
+        fn = std::sqrt(fn);
+        for (int64_t k = 0; k < nev; ++k) {
+            double* y = Y.data() + k * n;
+            double yn = 0.0;
+            for (int64_t i = 0; i < n; ++i) yn += y[i] * y[i];
+            yn = std::sqrt(yn);
+            if (yn > 0.0)
+                for (int64_t i = 0; i < n; ++i) y[i] /= yn;
+            double c = 0.0;
+            int64_t big = 0;
+            for (int64_t i = 0; i < n; ++i) {
+                c += y[i] * C.apps_f[i];
+                if (std::abs(y[i]) > std::abs(y[big])) big = i;
+            }
+            c = fn > 0.0 ? c / fn : 0.0;
+            const bool flip = std::abs(c) >= 1.0e-12 ? c < 0.0 : y[big] < 0.0;
+            if (flip) {
+                for (int64_t i = 0; i < n; ++i) y[i] = -y[i];
+                c = -c;
+            }
+            eigval[k] = R.theta[k];
+            resid[k] = R.resid[k];
+            corr[k] = c;
+        }
+        {
+            SyncCallGuard g;
+            DDPCA_HIP(hipMemcpy(h->apps.Y.p, Y.data(), Y.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+        h->apps.nev = (int)nev;
+        std::memcpy(h->apps.ms, R.ms, sizeof(R.ms));
+        if (info) {
+            info[0] = R.steps;
+            info[1] = R.restarts;
+            info[2] = R.applies;
+            info[3] = n;
+        }
+        if (!R.converged)
+            throw ApiError(DDPCA_ENOCONV, "mcontact_gpu_apps: not converged after " + std::to_string(R.restarts) +
+                                              " restarts (the best pairs are filled in)");
+    });
+}
+
+// Mode k of the last mcontact_gpu_apps on the owned subdomain tv, OUTP_SUB1(accuProl[tv] y_k's
+// rows of tv) (MCONTACT.h:2384-2393): the coarse correction's prolongation kernels into a zeroed
+// scratch with the workspace's layout, the hanging level by the rows the ADMM step applies after
+// a coarse correction
+int64_t mcontact_gpu_apps_mode(mcontact_t h, int64_t k, int64_t tv, double* out, int64_t cap) {
+    int64_t cnt = 0;
+    const int rc = guarded([&] {
+        if (!h) throw ApiError(DDPCA_EINVAL, "mcontact_gpu_apps_mode: NULL handle");
+        if (h->apps.nev < 1) throw ApiError(DDPCA_ESTATE, "mcontact_gpu_apps_mode: no mcontact_gpu_apps result");
+        if (k < 0 || k >= h->apps.nev) throw ApiError(DDPCA_EINVAL, "mcontact_gpu_apps_mode: mode index out of range");
+        const ddpca_mcontact::Sub* S = nullptr;
+        for (const auto& s : h->subs)
+            if (s.tv == tv) S = &s;
+        if (!S) throw ApiError(DDPCA_EINVAL, "subdomain not owned by this rank");
+        cnt = 3 * S->nn + S->nh;
+        if (!out) return;
+        select_device(h->device);
+        hipStream_t st = h->main;
+        DevBuf<double> scratch((size_t)(h->NU + h->NH));
+        scratch.zero(st);
+        coarse_prolong(*h, h->apps.Y.p + (size_t)k * h->cs.n, scratch.p);
+        if (h->NH) h->op_hang.apply(st, scratch.p, scratch.p + h->NU, nullptr);
+        DDPCA_HIP(hipStreamSynchronize(st));
+        SyncCallGuard g;
+        DDPCA_HIP(hipMemcpy(out, scratch.p + S->dof0, std::min(3 * S->nn, cap) * sizeof(double), hipMemcpyDeviceToHost));
+        if (cap > 3 * S->nn && S->nh)
+            DDPCA_HIP(hipMemcpy(out + 3 * S->nn, scratch.p + h->NU + S->hoff, std::min(S->nh, cap - 3 * S->nn) * sizeof(double),
+                                hipMemcpyDeviceToHost));
+    });
+    return rc < 0 ? rc : cnt;
+}
+
+int ddpca_eigs_orth_bench(int device, int64_t n, int m, int reps, double* out4) {
+    return guarded([&] {
+        if (!out4) throw ApiError(DDPCA_EINVAL, "ddpca_eigs_orth_bench: NULL output");
+        eigs_orth_bench(device, n, m, reps, out4);
+    });
 }
 
 int ddpca_mass_solve(int device, int64_t nsys, const ddpca_csr_t* A, const double* b, double* x, double rtol,

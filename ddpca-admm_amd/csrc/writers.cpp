@@ -103,4 +103,17 @@ int ddpca_write_resuStre(const char* path, const double* stre, int64_t nnodes) {
     });
 }
 
+// resuFreq.txt (MCONTACT::APPS, MCONTACT.h:2368-2377): eigenvalue and load correlation per mode
+int ddpca_write_resuFreq(const char* path, const double* eigval, const double* corr, int64_t nev) {
+    return guarded([&] {
+        if (nev < 0 || (nev > 0 && (!eigval || !corr))) throw ApiError(DDPCA_EINVAL, "ddpca_write_resuFreq: bad arguments");
+        File out(path);
+        for (int64_t k = 0; k < nev; ++k) {
+            out.num(eigval[k]);
+            out.num(corr[k]);
+            out.end();
+        }
+    });
+}
+
 }  // extern "C"

@@ -31,7 +31,7 @@ extern "C" {
 #define DDPCA_ESTATE (-4)   /* call sequence error */
 #define DDPCA_ECOMM (-5)    /* RCCL error */
 #define DDPCA_ENUMERIC (-6) /* NaN/Inf or breakdown in a Krylov scalar */
-#define DDPCA_ENOCONV (-7)  /* iteration cap reached before convergence (LAGRANGE's Newton loop) */
+#define DDPCA_ENOCONV (-7)  /* iteration cap reached before convergence (LAGRANGE's Newton loop, APPS's restarts) */
 
 /* last error message of the calling thread (never NULL) */
 const char* ddpca_last_error(void);
@@ -502,7 +502,11 @@ int64_t mcontact_gpu_monitor(mcontact_t h, double* out, int64_t cap_rows);
  * iterations of the last iterate call), "coarse_solve" (int64 x4: coarse rows, DOUBLE_M?, dense
  * bytes, dense fallback?), "gs_rows" (int64 x3: the fine rows the multicolour sweeps cover, the
  * band mode's ring and far rows -- 0, 0 without it), "gs_launch_bytes" (the sweeps' per-launch byte
- * model, doubles). */
+ * model, doubles), "apps_vec" (index = mode k of the last mcontact_gpu_apps: the coarse eigenvector
+ * y_k, n doubles, MCONTACT.h:2343-2403), "apps_timing" (doubles x5 of the last mcontact_gpu_apps: ms of its
+ * operator applications, orthogonalisation and Ritz products, filled when DDPCA_APPS_TIMING=1, then
+ * the coarse MGPIS's PCG iterations and recursive ||r|| / ||b|| in the last application, 0 with the
+ * dense inverse). */
 int64_t mcontact_gpu_get(mcontact_t h, const char* what, int64_t index, void* out, int64_t cap);
 /* Timing of the last iterate() call, summed over its iterations: [total_ms (host wall),
  * solve_ms (host wall of the body balance), iface_ms (device, interface step + monitor),
@@ -526,6 +530,41 @@ int64_t mcontact_gpu_bytes(mcontact_t h, double* out, int64_t cap);
  * copies min(7 N, cap) doubles when out != NULL.  DDPCA_EINVAL when tv is not owned by this rank
  * or the subdomain has no element tree (operator-level problems, ddpca_problem_set_subdomain). */
 int64_t mcontact_gpu_stress(mcontact_t h, ddpca_problem_t p, int64_t tv, double* out, int64_t cap);
+/* MCONTACT::APPS (MCONTACT.h:2343-2403, "automatic penalty parameter selection", SOLVE(appsCont =
+ * 0)): the nev eigenpairs of smallest magnitude of the interface-eliminated coarse operator
+ * globCoup_1 and each mode's correlation with the coarse load globForc_1.  The reference runs
+ * Spectra's SymEigsSolver on globCoup_1 (SmallestMagn, ncv = min(20 nev, n), tol 1e-6); here a
+ * thick-restart Lanczos iteration with full reorthogonalisation runs on the device-resident
+ * inverse (the dense potrf/potri inverse or DOUBLE_M_1's coarse MGPIS, whichever the handle
+ * holds), whose largest eigenvalues are the reciprocals of the wanted ones, from a fixed
+ * pseudo-random start vector, and stops on the TRUE residual of globCoup_1:
+ * resid[k] = ||A y_k - eigval[k] y_k|| / eigval[k] <= tol for every k, eigval[k] the Rayleigh
+ * quotient y_k . A y_k, checked every few steps.  ncv = 0: the reference's min(20 nev, n); tol = 0:
+ * the reference's 1e-6; at most max_restarts thick restarts (each keeps nev + (ncv - nev) / 2 Ritz
+ * vectors).  eigval[nev] ascending; corr[k] = y_k . globForc_1 / ||globForc_1|| with ||y_k|| = 1
+ * (MCONTACT.h:2366-2372).  Spectra leaves an eigenvector's sign open; here corr[k] >= 0, and where
+ * |corr[k]| < 1e-12 (a mode orthogonal to the load) the component of largest magnitude is
+ * positive.  info[4] (may be NULL) = {Lanczos steps, restarts, operator applications, n}.  The
+ * ADMM state (displacements, auxiliary vectors, multipliers, monitor rows) is not touched.
+ * DDPCA_ESTATE without an interface-eliminated coarse space (muscSett 0, or the LATIN-type space:
+ * the reference's own APPS returns -1 there, globCoup_1 being empty) or before the coarse operator
+ * is factorised; DDPCA_EINVAL for nev < 1, ncv <= nev, ncv > n, ncv > 512, or a handle of a
+ * multi-rank run (a rank holds only its own rows of the inverse); DDPCA_ENOCONV after
+ * max_restarts restarts, the best pairs filled in. */
+int mcontact_gpu_apps(mcontact_t h, int64_t nev, int64_t ncv, double tol, int64_t max_restarts,
+                      double* eigval, double* corr, double* resid, int64_t* info);
+/* Mode shape k of the last mcontact_gpu_apps on the owned subdomain tv (MCONTACT.h:2384-2393):
+ * OUTP_SUB1(accuProl[tv] y_k[baseReco[tv] ...]), computed on demand from the kept eigenvectors by
+ * the coarse correction's prolongation kernels into a zeroed scratch, in the layout of
+ * mcontact_gpu_get "resuDisp" (3 N in position numbering, then the hanging level, filled by the
+ * rows the ADMM step applies after a coarse correction; prescribed values on constrained dofs).
+ * Returns the count and copies min(count, cap) doubles when out != NULL. */
+int64_t mcontact_gpu_apps_mode(mcontact_t h, int64_t k, int64_t tv, double* out, int64_t cap);
+/* Measurement only (profiles/apps_probe.py; no reference counterpart; MCONTACT.h:2343-2403 has no
+ * such step, Spectra orthogonalises on the host): ms per Gram-Schmidt pass of an n-vector against
+ * m basis columns, out4[0] APPS's fused kernels, out4[1] the same pass composed from the GMRES
+ * driver's multi-dot and combination kernels, out4[2] the pass's algorithmic bytes. */
+int ddpca_eigs_orth_bench(int device, int64_t n, int m, int reps, double* out4);
 /* Measurement only (profiles/stress_probe.py; no reference counterpart): HIP-event times in ms of
  * the two kernels of the calling thread's last device stress recovery (ddpca_multigrid_stress
  * with device >= 0, mcontact_gpu_stress): out2[0] the element kernel, out2[1] the node kernel. */
@@ -617,6 +656,10 @@ int ddpca_write_resuMoni(const char* path, const double* rows, int64_t nrows, in
  * mcontact_gpu_stress return it (rows in the order the caller wants them: node ids through
  * posiNode on general trees). */
 int ddpca_write_resuStre(const char* path, const double* stre, int64_t nnodes);
+
+/* resuFreq.txt (MCONTACT::APPS, MCONTACT.h:2343-2403; the lines of 2368-2377): one line
+ * "eigenvalue correlation" per mode, as mcontact_gpu_apps returns them. */
+int ddpca_write_resuFreq(const char* path, const double* eigval, const double* corr, int64_t nev);
 
 #ifdef __cplusplus
 }
