@@ -190,6 +190,12 @@ def _declare(L: C.CDLL) -> None:
     L.mcontact_gpu_stress.argtypes = [_P, _P, C.c_int64, _P, C.c_int64]
     L.mcontact_gpu_stress.restype = C.c_int64
     L.ddpca_stress_last_kernel_ms.argtypes = [_DP]
+    L.ddpca_multigrid_stif.argtypes = [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _I64P]
+    L.ddpca_multigrid_volume.argtypes = [_P, C.c_int, _DP]
+    L.ddpca_multigrid_build_on.argtypes = [_P, _P, C.c_int]
+    L.ddpca_problem_set_assembly_device.argtypes = [_P, C.c_int]
+    L.ddpca_stif_last_kernel_ms.argtypes = [_DP]
+    L.ddpca_stif_last_host_ms.argtypes = [_DP]
     L.mgpis_gpu_vcycle.argtypes = [_P, _P, _P]
     L.mgpis_gpu_info.argtypes = [_P, _I64P]
     L.mgpis_gpu_vcycle_info.argtypes = [_P, C.c_char_p, C.c_int, _P, C.c_int64]
@@ -349,8 +355,12 @@ class Problem:
         self._keep_dole = d
         return self
 
-    def ESTABLISH(self, owner: Optional[Sequence[int]] = None, rank: int = 0) -> "Problem":
-        """MCONTACT::ESTABLISH; with owner/rank only this rank's subdomains are built."""
+    def ESTABLISH(self, owner: Optional[Sequence[int]] = None, rank: int = 0, assembly_device: int = -1) -> "Problem":
+        """MCONTACT::ESTABLISH; with owner/rank only this rank's subdomains are built.
+        assembly_device >= 0: STIF_MATR of every owned subdomain on that GPU
+        (ddpca_problem_set_assembly_device); -1: the host loop."""
+        if assembly_device >= 0:
+            _check(lib().ddpca_problem_set_assembly_device(self._h, int(assembly_device)))
         if owner is None:
             _check(lib().ddpca_problem_establish(self._h))
         else:
@@ -675,8 +685,11 @@ class TreeMultigrid:
                                          None if v is None else _ptr(v)))
         return self
 
-    def build(self) -> "TreeMultigrid":
-        _check(lib().ddpca_multigrid_build(self._h, None))
+    def build(self, device: int = -1) -> "TreeMultigrid":
+        """TRANSFER + PATCH + STIF_MATR + CONSTRAINT(1); device >= 0: STIF_MATR's values from the
+        kernels on that GPU; device < 0: the host loop (ddpca_multigrid_build_on, which is
+        ddpca_multigrid_build then)."""
+        _check(lib().ddpca_multigrid_build_on(self._h, None, int(device)))
         return self
 
     def view(self, what: str, level: int = 0) -> np.ndarray:
@@ -702,6 +715,31 @@ class TreeMultigrid:
         out = np.zeros((self.nnode, 7))
         _check(lib().ddpca_multigrid_stress(self._h, device, _ptr(u), _ptr(out)))
         return out
+
+
+    def stiffness(self, device: int = 0):
+        """MULTIGRID::STIF_MATR (MULTIGRID.h:950-1039) on the built tree: (ptr, col, val) of the nodal
+        stiffness as BSR3 over positions, val shaped nnzb x 3 x 3.  device < 0: the host element
+        loop; device >= 0: k_stif_elem / k_stif_gather (ddpca_multigrid_stif)."""
+        ptr, col, val, nb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().ddpca_multigrid_stif(self._h, int(device), C.byref(ptr), C.byref(col), C.byref(val), C.byref(nb)))
+
+        def copy(addr, count, dtype):
+            dtype = np.dtype(dtype)
+            if count == 0:
+                return np.zeros(0, dtype)
+            buf = (C.c_char * (count * dtype.itemsize)).from_address(addr.value)
+            return np.frombuffer(buf, dtype=dtype).copy()
+
+        p = copy(ptr, nb.value + 1, np.int64)
+        nnzb = int(p[-1])
+        return p, copy(col, nnzb, np.int32), copy(val, 9 * nnzb, np.float64).reshape(nnzb, 3, 3)
+
+    def volume(self, device: int = 0) -> float:
+        """MULTIGRID::GET_VOLUME (MULTIGRID.h:1041-1082) of the built tree's leaf elements."""
+        v = C.c_double()
+        _check(lib().ddpca_multigrid_volume(self._h, int(device), C.byref(v)))
+        return v.value
 
 
 # ============================================================================ device MGPIS
@@ -912,6 +950,22 @@ def stress_last_kernel_ms() -> tuple:
     out = (C.c_double * 2)()
     _check(lib().ddpca_stress_last_kernel_ms(out))
     return out[0], out[1]
+
+
+def stif_last_kernel_ms() -> tuple:
+    """HIP-event times (ms) of k_stif_elem and k_stif_gather of this thread's last device stiffness
+    assembly (ddpca_stif_last_kernel_ms; measurement only)."""
+    out = (C.c_double * 2)()
+    _check(lib().ddpca_stif_last_kernel_ms(out))
+    return out[0], out[1]
+
+
+def stif_last_host_ms() -> tuple:
+    """Host clock (ms) of the plan build, its upload (0 once cached) and the copy back of this thread's
+    last device stiffness assembly (ddpca_stif_last_host_ms; measurement only)."""
+    out = (C.c_double * 3)()
+    _check(lib().ddpca_stif_last_host_ms(out))
+    return out[0], out[1], out[2]
 
 
 def mass_solve(systems: Sequence, b: np.ndarray, rtol: float = 1e-14, maxit: int = 2000, fuse_alpha: int = -1,

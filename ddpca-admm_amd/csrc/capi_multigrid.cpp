@@ -8,6 +8,7 @@
 // MULTIGRID (oracle/ref_bind.hpp from_reference).
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <map>
 #include <set>
@@ -102,6 +103,59 @@ struct ddpca_curveds {
         return true;
     }
 };
+
+// ddpca_multigrid_build(_on): TRANSFER + PATCH, STIF_MATR (its element loop left to `values` when
+// given: the device assembly, capi_stif.hip), extra, CONSTRAINT(1)
+namespace ddpca {
+void multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra, const std::function<void(MULTIGRID&, double* val)>* values) {
+    ddpca_multigrid& M = open(h, false);
+    MULTIGRID& g = M.g;
+    if (!g.coupNode.empty() && g.coupReps < 0) throw ApiError(DDPCA_EINVAL, "coupled nodes need coupReps");
+    try {
+        g.force_general = true;
+        g.TRANSFER();  // TRANSFER + PATCH; node ids become positions (g.posiNode = earlTran)
+        if (values) g.STIF_MATR_BY(*values);
+        else g.STIF_MATR();
+        if (extra) {
+            // origStif[maxiLeve + 1] += extra in the node-id numbering (MCONTACT.h:816-822:
+            // the contact interfaces' systMass), moved to positions
+            if (extra->nrow != 3 * M.nnode || extra->ncol != 3 * M.nnode || (extra->nrow && !extra->ptr))
+                throw ApiError(DDPCA_EINVAL, "extra stiffness: 3N x 3N in node ids");
+            std::vector<int64_t> pos(M.nnode);
+            for (int64_t p = 0; p < M.nnode; ++p) pos[g.posiNode[p]] = p;
+            Csr A;
+            A.nrow = A.ncol = 3 * M.nnode;
+            std::vector<std::vector<std::pair<int32_t, double>>> rows(A.nrow);
+            for (int64_t r = 0; r < extra->nrow; ++r)
+                for (int64_t k = extra->ptr[r]; k < extra->ptr[r + 1]; ++k) {
+                    const int32_t c = extra->col[k];
+                    if (c < 0 || c >= A.ncol) throw ApiError(DDPCA_EINVAL, "extra stiffness: column out of range");
+                    rows[3 * pos[r / 3] + r % 3].push_back({(int32_t)(3 * pos[c / 3] + c % 3), extra->val[k]});
+                }
+            A.ptr.assign(A.nrow + 1, 0);
+            for (int64_t r = 0; r < A.nrow; ++r) {
+                for (const auto& e : rows[r]) {
+                    A.col.push_back(e.first);
+                    A.val.push_back(e.second);
+                }
+                A.ptr[r + 1] = (int64_t)A.col.size();
+            }
+            g.ADD_NODAL(A);
+        }
+        g.CONSTRAINT();
+    } catch (const ApiError&) {
+        throw;
+    } catch (const std::invalid_argument& e) {
+        throw ApiError(DDPCA_EINVAL, e.what());
+    } catch (const std::runtime_error& e) {
+        throw ApiError(DDPCA_EINVAL, e.what());
+    }
+    M.coords_by_id.assign(3 * M.nnode, 0.0);
+    for (int64_t p = 0; p < M.nnode; ++p)
+        for (int a = 0; a < 3; ++a) M.coords_by_id[3 * g.posiNode[p] + a] = g.nodeCoor[p][a];
+    M.built = true;
+}
+}  // namespace ddpca
 
 extern "C" {
 
@@ -363,53 +417,7 @@ int ddpca_multigrid_tree(ddpca_multigrid_t h, const char* what, const void** dat
 }
 
 int ddpca_multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra) {
-    return guarded([&] {
-        ddpca_multigrid& M = open(h, false);
-        MULTIGRID& g = M.g;
-        if (!g.coupNode.empty() && g.coupReps < 0) throw ApiError(DDPCA_EINVAL, "coupled nodes need coupReps");
-        try {
-            g.force_general = true;
-            g.TRANSFER();  // TRANSFER + PATCH; node ids become positions (g.posiNode = earlTran)
-            g.STIF_MATR();
-            if (extra) {
-                // origStif[maxiLeve + 1] += extra in the node-id numbering (MCONTACT.h:816-822:
-                // the contact interfaces' systMass), moved to positions
-                if (extra->nrow != 3 * M.nnode || extra->ncol != 3 * M.nnode || (extra->nrow && !extra->ptr))
-                    throw ApiError(DDPCA_EINVAL, "extra stiffness: 3N x 3N in node ids");
-                std::vector<int64_t> pos(M.nnode);
-                for (int64_t p = 0; p < M.nnode; ++p) pos[g.posiNode[p]] = p;
-                Csr A;
-                A.nrow = A.ncol = 3 * M.nnode;
-                std::vector<std::vector<std::pair<int32_t, double>>> rows(A.nrow);
-                for (int64_t r = 0; r < extra->nrow; ++r)
-                    for (int64_t k = extra->ptr[r]; k < extra->ptr[r + 1]; ++k) {
-                        const int32_t c = extra->col[k];
-                        if (c < 0 || c >= A.ncol) throw ApiError(DDPCA_EINVAL, "extra stiffness: column out of range");
-                        rows[3 * pos[r / 3] + r % 3].push_back({(int32_t)(3 * pos[c / 3] + c % 3), extra->val[k]});
-                    }
-                A.ptr.assign(A.nrow + 1, 0);
-                for (int64_t r = 0; r < A.nrow; ++r) {
-                    for (const auto& e : rows[r]) {
-                        A.col.push_back(e.first);
-                        A.val.push_back(e.second);
-                    }
-                    A.ptr[r + 1] = (int64_t)A.col.size();
-                }
-                g.ADD_NODAL(A);
-            }
-            g.CONSTRAINT();
-        } catch (const ApiError&) {
-            throw;
-        } catch (const std::invalid_argument& e) {
-            throw ApiError(DDPCA_EINVAL, e.what());
-        } catch (const std::runtime_error& e) {
-            throw ApiError(DDPCA_EINVAL, e.what());
-        }
-        M.coords_by_id.assign(3 * M.nnode, 0.0);
-        for (int64_t p = 0; p < M.nnode; ++p)
-            for (int a = 0; a < 3; ++a) M.coords_by_id[3 * g.posiNode[p] + a] = g.nodeCoor[p][a];
-        M.built = true;
-    });
+    return guarded([&] { multigrid_build(h, extra, nullptr); });
 }
 
 int ddpca_multigrid_view(ddpca_multigrid_t h, const char* what, int64_t level, const void** data, int64_t* count,

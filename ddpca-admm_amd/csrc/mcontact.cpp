@@ -306,6 +306,17 @@ void MCONTACT::ESTABLISH(const std::vector<uint8_t>* owned) {
         Interface& itf = searCont[ts];
         if (mine(itf.body[0]) || mine(itf.body[1])) itf.BUILD(multGrid[itf.body[0]], multGrid[itf.body[1]]);
     }
+    // the device assembly (stifValues): one subdomain after the other on the one GPU, before the
+    // host threads share out the rest
+    std::vector<double> t_stif(nsub, 0.0);
+    if (stifValues)
+        for (int64_t tv = 0; tv < nsub; ++tv) {
+            if (!mine(tv)) continue;
+            const auto t0 = std::chrono::steady_clock::now();
+            multGrid[tv].STIF_MATR_BY(stifValues);
+            multGrid[tv].stifPlan.reset();  // assembled once: the plan and its device copy are not kept
+            t_stif[tv] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
 #pragma omp parallel for schedule(dynamic, 1)
     for (int64_t tv = 0; tv < nsub; ++tv) {
         if (!mine(tv)) continue;
@@ -313,7 +324,7 @@ void MCONTACT::ESTABLISH(const std::vector<uint8_t>* owned) {
         const bool verbose = std::getenv("DDPCA_VERBOSE") != nullptr;
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto t1 = now();
-        g.STIF_MATR();
+        if (!stifValues) g.STIF_MATR();
         auto t2 = now();
         for (const auto& itf : searCont)
             for (int s = 0; s < 2; ++s)
@@ -327,7 +338,7 @@ void MCONTACT::ESTABLISH(const std::vector<uint8_t>* owned) {
         if (verbose) {
             auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
             std::fprintf(stderr, "[ddpca] establish sd %ld: transfer %.0f ms, stif %.0f ms, systMass %.0f ms, constraint %.0f ms\n",
-                         (long)tv, t_transfer[tv], ms(t1, t2), ms(t2, t3), ms(t3, t4));
+                         (long)tv, t_transfer[tv], stifValues ? t_stif[tv] : ms(t1, t2), ms(t2, t3), ms(t3, t4));
         }
     }
     // ---- coarse space (MCONTACT.h:858-863)

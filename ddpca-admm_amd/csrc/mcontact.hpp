@@ -93,6 +93,9 @@ public:
     // per-subdomain mask; only owned bodies and interfaces touching them are built (one rank's
     // share of a multi-GPU run).
     void ESTABLISH(const std::vector<uint8_t>* owned = nullptr);
+    // set (ddpca_problem_set_assembly_device): ESTABLISH assembles every owned subdomain's
+    // stiffness through it, in a serial pass before the loop over subdomains (STIF_MATR_BY)
+    std::function<void(MULTIGRID&, double* val)> stifValues;
     double GET_CHAR_LENG() const;  // MCONTACT.h:2478-2491
 };
 

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <mutex>
 #include <stdexcept>
 #include <omp.h>
 
@@ -368,6 +369,7 @@ void MULTIGRID::REFINE(std::set<int64_t>& split, const std::map<int64_t, std::se
 void MULTIGRID::TRANSFER() {
     const int64_t N = numNodes();
     strePlan.reset();
+    stifPlan.reset();
     hangMap.clear();
     // uniform refinement of a generator (REFINE_ALL, no coupling): node ids are already the
     // reference's positions and every new node's parents are recorded -- the fast path below is
@@ -631,13 +633,13 @@ void MULTIGRID::TRANSFER_GENERAL() {
 
 // ---------------------------------------------------------------------------------- stiffness
 void MULTIGRID::STIF_MATR() {
-    const int64_t N = numNodes();
-    const double lam = mateElas * matePois / (1.0 + matePois) / (1.0 - 2.0 * matePois);
-    const double mu = mateElas / 2.0 / (1.0 + matePois);
-    double D[6][6] = {};
-    for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b) D[a][b] = lam + (a == b ? 2.0 * mu : 0.0);
-    D[3][3] = D[4][4] = D[5][5] = mu;
+    const StifColours c = STIF_COLOURS();
+    STIF_PATTERN(c, origStif);
+    STIF_VALUES(c, origStif);
+}
+
+StifColours MULTIGRID::STIF_COLOURS() const {
+    StifColours out;
     std::vector<int64_t> leaves;
     for (int64_t e = 0; e < (int64_t)elemVect.size(); ++e)
         if (elemVect[e].leaf()) leaves.push_back(e);
@@ -653,7 +655,8 @@ void MULTIGRID::STIF_MATR() {
         if (h < 0) h = ext;
         if (ext != h) uniform = false;
     }
-    std::vector<std::vector<int64_t>> colour(uniform ? 8 : 1);
+    std::vector<std::vector<int64_t>>& colour = out.list;
+    colour.assign(uniform ? 8 : 1, {});
     for (int64_t e : leaves) {
         if (!uniform) { colour[0].push_back(e); continue; }
         int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX};
@@ -661,6 +664,14 @@ void MULTIGRID::STIF_MATR() {
             for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], nodeLatt[elemVect[e].cornNode[k]][a]);
         colour[((lo[0] / h) & 1) | (((lo[1] / h) & 1) << 1) | (((lo[2] / h) & 1) << 2)].push_back(e);
     }
+    out.uniform = uniform;
+    return out;
+}
+
+void MULTIGRID::STIF_PATTERN(const StifColours& c, Bsr3& K) const {
+    const int64_t N = numNodes();
+    const bool uniform = c.uniform;
+    const auto& colour = c.list;
     // node adjacency (nodes sharing a leaf element): flat buffer of 64 candidates per node,
     // filled colour by colour (no two elements of a colour share a node), then sort + unique
     {
@@ -683,15 +694,26 @@ void MULTIGRID::STIF_MATR() {
             std::sort(b, b + cnt[i]);
             cnt[i] = (int32_t)(std::unique(b, b + cnt[i]) - b);
         }
-        origStif = Bsr3();
-        origStif.nb = origStif.mb = N;
-        origStif.ptr.assign(N + 1, 0);
-        for (int64_t i = 0; i < N; ++i) origStif.ptr[i + 1] = origStif.ptr[i] + cnt[i];
-        origStif.col.resize(origStif.ptr[N]);
+        K = Bsr3();
+        K.nb = K.mb = N;
+        K.ptr.assign(N + 1, 0);
+        for (int64_t i = 0; i < N; ++i) K.ptr[i + 1] = K.ptr[i] + cnt[i];
+        K.col.resize(K.ptr[N]);
 #pragma omp parallel for schedule(static)
-        for (int64_t i = 0; i < N; ++i) std::copy(&flat[i * 64], &flat[i * 64] + cnt[i], origStif.col.begin() + origStif.ptr[i]);
-        origStif.val.assign(9 * origStif.ptr[N], 0.0);
+        for (int64_t i = 0; i < N; ++i) std::copy(&flat[i * 64], &flat[i * 64] + cnt[i], K.col.begin() + K.ptr[i]);
+        K.val.assign(9 * K.ptr[N], 0.0);
     }
+}
+
+void MULTIGRID::STIF_VALUES(const StifColours& c, Bsr3& K) const {
+    const double lam = mateElas * matePois / (1.0 + matePois) / (1.0 - 2.0 * matePois);
+    const double mu = mateElas / 2.0 / (1.0 + matePois);
+    double D[6][6] = {};
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) D[a][b] = lam + (a == b ? 2.0 * mu : 0.0);
+    D[3][3] = D[4][4] = D[5][5] = mu;
+    const bool uniform = c.uniform;
+    const auto& colour = c.list;
     for (const auto& list : colour) {
 #pragma omp parallel if (uniform)
         {
@@ -722,11 +744,11 @@ void MULTIGRID::STIF_MATR() {
                 }
                 for (int a = 0; a < 8; ++a) {
                     const int64_t r = el.cornNode[a];
-                    const int32_t* cb = &origStif.col[origStif.ptr[r]];
-                    const int64_t len = origStif.ptr[r + 1] - origStif.ptr[r];
+                    const int32_t* cb = &K.col[K.ptr[r]];
+                    const int64_t len = K.ptr[r + 1] - K.ptr[r];
                     for (int b = 0; b < 8; ++b) {
-                        const int64_t pos = origStif.ptr[r] + (std::lower_bound(cb, cb + len, (int32_t)el.cornNode[b]) - cb);
-                        double* blk = origStif.block(pos);
+                        const int64_t pos = K.ptr[r] + (std::lower_bound(cb, cb + len, (int32_t)el.cornNode[b]) - cb);
+                        double* blk = K.block(pos);
                         for (int i = 0; i < 3; ++i)
                             for (int j = 0; j < 3; ++j) blk[3 * i + j] += KE[3 * a + i][3 * b + j];
                     }
@@ -754,6 +776,55 @@ double MULTIGRID::GET_VOLUME() const {
     double v = 0.0;
     for (double x : pv) v += x;
     return v;
+}
+
+const StifPlan& MULTIGRID::STIF_PLAN() {
+    static std::mutex plan_mutex;
+    std::lock_guard<std::mutex> lock(plan_mutex);
+    if (stifPlan) return *stifPlan;
+    const int64_t N = numNodes();
+    if (elemVect.empty() || N == 0) throw std::invalid_argument("STIF_PLAN: the subdomain has no element tree");
+    if (leveCount.empty() || nodalCount() != N) throw std::invalid_argument("STIF_PLAN: TRANSFER has not run on this tree");
+    if (N >= (int64_t)1 << 31) throw std::invalid_argument("STIF_PLAN: nodes must fit int32");
+    auto P = std::make_shared<StifPlan>();
+    P->nnode = N;
+    for (const auto& e : elemVect) {
+        if (!e.leaf()) continue;
+        for (int64_t c : e.cornNode) {
+            if (c < 0 || c >= N) throw std::invalid_argument("STIF_PLAN: corner node out of range");
+            P->corner.push_back((int32_t)c);
+        }
+    }
+    P->nleaf = (int64_t)P->corner.size() / 8;
+    if (P->nleaf == 0) throw std::invalid_argument("STIF_PLAN: the tree has no leaf element");
+    if (P->nleaf >= (int64_t)1 << 28) throw std::invalid_argument("STIF_PLAN: leaf << 3 | corner must fit int32");
+    STIF_PATTERN(STIF_COLOURS(), P->K);
+    P->K.val.clear();
+    P->K.val.shrink_to_fit();
+    if (P->K.nnzb() >= (int64_t)1 << 31) throw std::invalid_argument("STIF_PLAN: stored blocks must fit int32");
+    P->brow.resize(P->K.nnzb());
+    for (int64_t r = 0; r < N; ++r)
+        for (int64_t k = P->K.ptr[r]; k < P->K.ptr[r + 1]; ++k) P->brow[k] = (int32_t)r;
+    // node -> incident (leaf, corner) by counting sort over the leaves in order: ascending leaf
+    // within a node, ascending corner within a leaf
+    P->n2ePtr.assign(N + 1, 0);
+    for (int32_t c : P->corner) P->n2ePtr[c + 1]++;
+    for (int64_t i = 0; i < N; ++i) P->n2ePtr[i + 1] += P->n2ePtr[i];
+    P->n2eInc.resize(P->n2ePtr[N]);
+    std::vector<int64_t> fill(P->n2ePtr.begin(), P->n2ePtr.end() - 1);
+    for (int64_t l = 0; l < P->nleaf; ++l)
+        for (int a = 0; a < 8; ++a) P->n2eInc[fill[P->corner[8 * l + a]]++] = (int32_t)(l << 3 | a);
+    stifPlan = std::move(P);
+    return *stifPlan;
+}
+
+void MULTIGRID::STIF_MATR_BY(const std::function<void(MULTIGRID&, double* val)>& values) {
+    const StifPlan& P = STIF_PLAN();
+    origStif.nb = origStif.mb = P.nnode;
+    origStif.ptr = P.K.ptr;
+    origStif.col = P.K.col;
+    origStif.val.resize(9 * origStif.ptr[P.nnode]);  // `values` writes every stored block
+    values(*this, origStif.val.data());
 }
 
 void MULTIGRID::ADD_NODAL(const Csr& A) {

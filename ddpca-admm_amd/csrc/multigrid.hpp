@@ -28,6 +28,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <set>
@@ -61,6 +62,26 @@ struct StressPlan {
     std::vector<int32_t> rotIndex;  // nnode: index into rot of a nodeRota node, else -1
     std::vector<double> rot;        // 9 per rotated node, row-major
     std::shared_ptr<void> device;   // the device copy (device_stress.hip), made on first use
+};
+
+// What the device assembly of STIF_MATR needs besides the coordinates (STIF_PLAN): the leaf
+// elements' corners, the stiffness pattern (the host's own: STIF_PATTERN), and per node its incident
+// leaf elements in ascending leaf order, the order in which the host's general path adds them.
+struct StifPlan {
+    int64_t nnode = 0, nleaf = 0;
+    std::vector<int32_t> corner;   // 8 nleaf: corner positions of leaf element l (elemVect order)
+    Bsr3 K;                        // ptr / col: the pattern of origStif; val: the last ddpca_multigrid_stif
+    std::vector<int32_t> brow;     // nnzb: the block row of stored block k (K.ptr expanded)
+    std::vector<int64_t> n2ePtr;   // nnode + 1: incidences of node p are [n2ePtr[p], n2ePtr[p + 1])
+    std::vector<int32_t> n2eInc;   // incidence: leaf << 3 | local corner, leaves ascending
+    std::shared_ptr<void> device;  // the device copy (device_stif.hip), made on first use
+};
+
+// The leaf elements of STIF_MATR in the lists its loops run over: the eight lattice colours of a
+// uniform tree (no two elements of a colour share a node: the OpenMP loops), else one list.
+struct StifColours {
+    bool uniform = false;
+    std::vector<std::vector<int64_t>> list;
 };
 
 class MULTIGRID {
@@ -133,7 +154,18 @@ public:
     double mateElas = 210.0e9;
     double matePois = 0.3;
     Bsr3 origStif;  // full nodal stiffness (reference origStif[maxiLeve + 1])
-    void STIF_MATR();
+    void STIF_MATR();  // STIF_PATTERN + STIF_VALUES on origStif
+    // the two halves of STIF_MATR: the node adjacency (K.ptr / K.col, K.val zeroed; "node in more
+    // than 8 elements" is checked here) and the element loop that adds into K.val
+    StifColours STIF_COLOURS() const;
+    void STIF_PATTERN(const StifColours& c, Bsr3& K) const;
+    void STIF_VALUES(const StifColours& c, Bsr3& K) const;
+    // STIF_MATR with the element loop left to `values` (the device assembly, device_stif.hip):
+    // origStif takes the plan's pattern and the values it writes (9 per stored block)
+    void STIF_MATR_BY(const std::function<void(MULTIGRID&, double* val)>& values);
+    // the device assembly's plan on the tree after TRANSFER / PATCH, built once and kept
+    std::shared_ptr<StifPlan> stifPlan;
+    const StifPlan& STIF_PLAN();
     double GET_VOLUME() const;
     // origStif += A (A given as scalar CSR on the 3N nodal dofs, pattern inside node adjacency)
     void ADD_NODAL(const Csr& A);

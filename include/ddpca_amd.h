@@ -397,6 +397,37 @@ int ddpca_problem_set_subdomain_multigrid(ddpca_problem_t p, int64_t tv, ddpca_m
  * GPU (the plan is uploaded on the first call and kept with g); device < 0: the host restatement
  * (OpenMP).  DDPCA_EINVAL for a NULL argument or a multigrid that is not built. */
 int ddpca_multigrid_stress(ddpca_multigrid_t g, int device, const double* disp, double* stre);
+/* MULTIGRID::STIF_MATR (MULTIGRID.h:950-1039) on the built tree: the nodal stiffness
+ * origStif[maxiLeve + 1], reassembled from the tree's coordinates after PATCH and its material, as
+ * BSR3 over positions: *nb block rows, ptr[*nb + 1], col[ptr[*nb]], val 9 doubles per stored block,
+ * row-major.  The arrays are owned by g until the next call; none of the tree's operators changes.
+ * The pattern is the host's in both cases.  device < 0: the host element loop; device >= 0: the
+ * fp64 kernels k_stif_elem / k_stif_gather on that GPU (the plan is uploaded on the first call and
+ * kept with g; 4608 bytes of device memory per leaf element for the length of the call -- when the
+ * allocation fails the call returns DDPCA_EHIP and the message names the size; there is no host
+ * fallback).  Two device calls return the same bits.  DDPCA_EINVAL for a NULL argument or a
+ * multigrid that is not built. */
+int ddpca_multigrid_stif(ddpca_multigrid_t g, int device, const int64_t** ptr, const int32_t** col, const double** val,
+                         int64_t* nb);
+/* MULTIGRID::GET_VOLUME (MULTIGRID.h:1041-1082): the volume of the leaf elements, sum_g w_g det J
+ * over the 27 Gauss points, on the host (device < 0) or by the element kernel and a fixed-order
+ * reduction (device >= 0).  Errors as ddpca_multigrid_stif. */
+int ddpca_multigrid_volume(ddpca_multigrid_t g, int device, double* volume);
+/* ddpca_multigrid_build (MULTIGRID.h:722-1255) with the values of STIF_MATR (950-1039) from the
+ * kernels of ddpca_multigrid_stif when device >= 0; extra, ADD_NODAL and CONSTRAINT(1) run on the
+ * host as in ddpca_multigrid_build, on the downloaded values.  device < 0 is ddpca_multigrid_build. */
+int ddpca_multigrid_build_on(ddpca_multigrid_t g, const ddpca_csr_t* extra, int device);
+/* Before ddpca_problem_establish(_owned): MCONTACT::ESTABLISH (MCONTACT.h:812-825) assembles every
+ * owned subdomain's STIF_MATR on GPU `device`, one subdomain after the other before the host loop
+ * over the subdomains, which keeps ADD_NODAL and CONSTRAINT(1) (DDPCA_VERBOSE's "stif" column then
+ * times the device pass).  device < 0 (the default): the host loop.  DDPCA_ESTATE once the problem
+ * is established. */
+int ddpca_problem_set_assembly_device(ddpca_problem_t p, int device);
+/* Measurement only (profiles/stif_probe.py; no reference counterpart), of the calling thread's
+ * last device assembly: out2 = HIP-event times in ms of k_stif_elem and k_stif_gather; out3 = host
+ * clock in ms of the plan build, its upload (both 0 once cached) and the copy back of the values. */
+int ddpca_stif_last_kernel_ms(double* out2);
+int ddpca_stif_last_host_ms(double* out3);
 /* The whole MCONTACT::ESTABLISH (MCONTACT.h:181-896) from element trees: subdomain tv of an empty
  * problem (ddpca_problem_empty) takes a copy of the UNBUILT multigrid g (its tree and the inputs
  * set with ddpca_multigrid_set: constraints, loads, rotations, coupled nodes, material);
