@@ -196,6 +196,13 @@ def _declare(L: C.CDLL) -> None:
     L.ddpca_problem_set_assembly_device.argtypes = [_P, C.c_int]
     L.ddpca_stif_last_kernel_ms.argtypes = [_DP]
     L.ddpca_stif_last_host_ms.argtypes = [_DP]
+    L.ddpca_galerkin_rap.argtypes = [C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.POINTER(_P)]
+    L.ddpca_galerkin_view.argtypes = [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _I64P]
+    L.ddpca_galerkin_destroy.argtypes = [_P]
+    L.ddpca_multigrid_build_with.argtypes = [_P, _P, C.c_int, C.c_int]
+    L.ddpca_problem_set_galerkin_device.argtypes = [_P, C.c_int]
+    L.ddpca_galerkin_last_ms.argtypes = [_DP]
+    L.ddpca_galerkin_last_level_ms.argtypes = [_DP, C.c_int64]
     L.mgpis_gpu_vcycle.argtypes = [_P, _P, _P]
     L.mgpis_gpu_info.argtypes = [_P, _I64P]
     L.mgpis_gpu_vcycle_info.argtypes = [_P, C.c_char_p, C.c_int, _P, C.c_int64]
@@ -355,12 +362,17 @@ class Problem:
         self._keep_dole = d
         return self
 
-    def ESTABLISH(self, owner: Optional[Sequence[int]] = None, rank: int = 0, assembly_device: int = -1) -> "Problem":
+    def ESTABLISH(self, owner: Optional[Sequence[int]] = None, rank: int = 0, assembly_device: int = -1,
+                  galerkin_device: int = -1) -> "Problem":
         """MCONTACT::ESTABLISH; with owner/rank only this rank's subdomains are built.
         assembly_device >= 0: STIF_MATR of every owned subdomain on that GPU
-        (ddpca_problem_set_assembly_device); -1: the host loop."""
+        (ddpca_problem_set_assembly_device); -1: the host loop.  galerkin_device >= 0: the Galerkin
+        chain of every owned subdomain's CONSTRAINT on that GPU (ddpca_problem_set_galerkin_device);
+        -1: galerkin_rap on the host."""
         if assembly_device >= 0:
             _check(lib().ddpca_problem_set_assembly_device(self._h, int(assembly_device)))
+        if galerkin_device >= 0:
+            _check(lib().ddpca_problem_set_galerkin_device(self._h, int(galerkin_device)))
         if owner is None:
             _check(lib().ddpca_problem_establish(self._h))
         else:
@@ -685,11 +697,15 @@ class TreeMultigrid:
                                          None if v is None else _ptr(v)))
         return self
 
-    def build(self, device: int = -1) -> "TreeMultigrid":
+    def build(self, device: int = -1, galerkin_device: int = -1) -> "TreeMultigrid":
         """TRANSFER + PATCH + STIF_MATR + CONSTRAINT(1); device >= 0: STIF_MATR's values from the
         kernels on that GPU; device < 0: the host loop (ddpca_multigrid_build_on, which is
-        ddpca_multigrid_build then)."""
-        _check(lib().ddpca_multigrid_build_on(self._h, None, int(device)))
+        ddpca_multigrid_build then).  galerkin_device >= 0: CONSTRAINT's Galerkin chain by k_rap on
+        that GPU (ddpca_multigrid_build_with); < 0: galerkin_rap on the host."""
+        if galerkin_device >= 0:
+            _check(lib().ddpca_multigrid_build_with(self._h, None, int(device), int(galerkin_device)))
+        else:
+            _check(lib().ddpca_multigrid_build_on(self._h, None, int(device)))
         return self
 
     def view(self, what: str, level: int = 0) -> np.ndarray:
@@ -966,6 +982,65 @@ def stif_last_host_ms() -> tuple:
     out = (C.c_double * 3)()
     _check(lib().ddpca_stif_last_host_ms(out))
     return out[0], out[1], out[2]
+
+
+def galerkin_rap(A_ptr, A_col, A_val, S_ptr, S_col, S_w, nc: int, bent=None, bval=None, device: int = 0):
+    """The Galerkin product of MULTIGRID::CONSTRAINT (MULTIGRID.h:1182-1184), C = P^T A P: A as
+    BSR3 on the fine nodes (A_val: 9 per block, row-major), P = S (x) I3 from the node stencil S
+    (len(S_ptr) - 1 fine nodes x nc coarse nodes) whose entries bent (ascending indices into S_col)
+    are the full 3 x 3 blocks bval instead of w I.  Returns (ptr, col, val[nnzb, 3, 3]) of C.
+    device < 0: the host's galerkin_rap; device >= 0: k_rap on that GPU (ddpca_galerkin_rap)."""
+    ap = np.ascontiguousarray(A_ptr, dtype=np.int64)
+    ac = np.ascontiguousarray(A_col, dtype=np.int32)
+    av = np.ascontiguousarray(A_val, dtype=np.float64).reshape(-1)
+    sp = np.ascontiguousarray(S_ptr, dtype=np.int64)
+    sc = np.ascontiguousarray(S_col, dtype=np.int32)
+    sw = np.ascontiguousarray(S_w, dtype=np.float64)
+    nf = len(sp) - 1
+    if len(ap) != nf + 1 or len(av) != 9 * len(ac) or len(sw) != len(sc):
+        raise ValueError("galerkin_rap: A and S need nf + 1 row pointers each, 9 values per block of A, one weight per entry of S")
+    if nf < 0 or int(ap[-1]) > len(ac) or int(sp[-1]) > len(sc):
+        raise ValueError("galerkin_rap: the row pointers end past the entries given")
+    be = np.zeros(0, np.int64) if bent is None else np.ascontiguousarray(bent, dtype=np.int64)
+    bv = np.zeros(0) if bval is None else np.ascontiguousarray(bval, dtype=np.float64).reshape(-1)
+    if len(bv) != 9 * len(be):
+        raise ValueError("galerkin_rap: bval needs 9 values per entry of bent")
+    h = C.c_void_p()
+    _check(lib().ddpca_galerkin_rap(int(device), nf, int(nc), _ptr(ap), _ptr(ac), _ptr(av), _ptr(sp), _ptr(sc), _ptr(sw),
+                                    len(be), _ptr(be) if len(be) else None, _ptr(bv) if len(be) else None, C.byref(h)))
+    try:
+        ptr, col, val, nb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int64()
+        _check(lib().ddpca_galerkin_view(h, C.byref(ptr), C.byref(col), C.byref(val), C.byref(nb)))
+
+        def copy(addr, count, dtype):
+            dtype = np.dtype(dtype)
+            if count == 0:
+                return np.zeros(0, dtype)
+            buf = (C.c_char * (count * dtype.itemsize)).from_address(addr.value)
+            return np.frombuffer(buf, dtype=dtype).copy()
+
+        p = copy(ptr, nb.value + 1, np.int64)
+        nnzb = int(p[-1])
+        return p, copy(col, nnzb, np.int32), copy(val, 9 * nnzb, np.float64).reshape(nnzb, 3, 3)
+    finally:
+        lib().ddpca_galerkin_destroy(h)
+
+
+def galerkin_last_ms() -> tuple:
+    """Of this thread's last device Galerkin chain (ddpca_galerkin_last_ms; measurement only), in ms:
+    host clock of the pattern build and of the uploads, HIP-event time of the kernels summed over the
+    levels, host clock of the copies back (with the sizing of the host arrays they fill)."""
+    out = (C.c_double * 4)()
+    _check(lib().ddpca_galerkin_last_ms(out))
+    return tuple(out)
+
+
+def galerkin_last_level_ms() -> tuple:
+    """The kernel time (ms, HIP events) of each product of this thread's last device Galerkin chain,
+    in the chain's order (ddpca_galerkin_last_level_ms; measurement only)."""
+    out = (C.c_double * 64)()
+    n = _check(lib().ddpca_galerkin_last_level_ms(out, 64))
+    return tuple(out[:n])
 
 
 def mass_solve(systems: Sequence, b: np.ndarray, rtol: float = 1e-14, maxit: int = 2000, fuse_alpha: int = -1,

@@ -105,9 +105,11 @@ struct ddpca_curveds {
 };
 
 // ddpca_multigrid_build(_on): TRANSFER + PATCH, STIF_MATR (its element loop left to `values` when
-// given: the device assembly, capi_stif.hip), extra, CONSTRAINT(1)
+// given: the device assembly, capi_stif.hip), extra, CONSTRAINT(1) (its Galerkin chain left to
+// `galerkin` when given: the device products, capi_galerkin.hip)
 namespace ddpca {
-void multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra, const std::function<void(MULTIGRID&, double* val)>* values) {
+void multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra, const std::function<void(MULTIGRID&, double* val)>* values,
+                     const GalerkinChain* galerkin) {
     ddpca_multigrid& M = open(h, false);
     MULTIGRID& g = M.g;
     if (!g.coupNode.empty() && g.coupReps < 0) throw ApiError(DDPCA_EINVAL, "coupled nodes need coupReps");
@@ -142,6 +144,7 @@ void multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra, const std::f
             }
             g.ADD_NODAL(A);
         }
+        if (galerkin) g.galerkinChain = *galerkin;
         g.CONSTRAINT();
     } catch (const ApiError&) {
         throw;
@@ -417,7 +420,7 @@ int ddpca_multigrid_tree(ddpca_multigrid_t h, const char* what, const void** dat
 }
 
 int ddpca_multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra) {
-    return guarded([&] { multigrid_build(h, extra, nullptr); });
+    return guarded([&] { multigrid_build(h, extra, nullptr, nullptr); });
 }
 
 int ddpca_multigrid_view(ddpca_multigrid_t h, const char* what, int64_t level, const void** data, int64_t* count,
@@ -450,7 +453,10 @@ int ddpca_multigrid_view(ddpca_multigrid_t h, const char* what, int64_t level, c
         else if (w == "consFlag") put(g.consFlag, data, count, dtype);
         else if (w == "consForc") put(g.consForc, data, count, dtype);
         else if (w == "dispForc") put(g.dispForc, data, count, dtype);
-        else if (w.rfind("K:", 0) == 0) {  // MGPIS::consStif[level]
+        else if (w == "galerkinMs") {  // host clock of the build's Galerkin chain (measurement only)
+            M.f64 = {g.galerkinMs};
+            put(M.f64, data, count, dtype);
+        } else if (w.rfind("K:", 0) == 0) {  // MGPIS::consStif[level]
             lev(0, L);
             M.csr = g.consStif(level);
             csr_part(w.substr(2));

@@ -49,6 +49,10 @@ MULTIGRID& built_tree(ddpca_multigrid_t h, bool args_ok, const char* who) {
 
 }  // namespace
 
+namespace ddpca {
+std::function<void(MULTIGRID&, double* val)> stif_device_values(int device) { return device_values(device); }
+}  // namespace ddpca
+
 extern "C" {
 
 int ddpca_stif_last_kernel_ms(double* out2) {

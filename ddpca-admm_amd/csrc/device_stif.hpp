@@ -23,8 +23,13 @@ void stif_device(MULTIGRID& g, int device, double* val, double* volume, double m
 double volume_device(MULTIGRID& g, int device);
 
 // ddpca_multigrid_build with STIF_MATR's element loop left to `values` when given
-// (capi_multigrid.cpp; throws ApiError)
-void multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra, const std::function<void(MULTIGRID&, double* val)>* values);
+// and CONSTRAINT's Galerkin chain left to `galerkin` when given (capi_multigrid.cpp; throws ApiError)
+void multigrid_build(ddpca_multigrid_t h, const ddpca_csr_t* extra, const std::function<void(MULTIGRID&, double* val)>* values,
+                     const GalerkinChain* galerkin = nullptr);
+
+// the element loop of STIF_MATR on `device` as STIF_MATR_BY takes it (capi_stif.hip: it selects the
+// device, builds the plan when g has none and keeps the times of ddpca_stif_last_*_ms)
+std::function<void(MULTIGRID&, double* val)> stif_device_values(int device);
 
 constexpr int kStifElemDoubles = 576;  // 8 x 8 blocks of 9, every block stored (no symmetry)
 

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <exception>
 #include <map>
 #include <numeric>
 #include <stdexcept>
@@ -317,6 +318,7 @@ void MCONTACT::ESTABLISH(const std::vector<uint8_t>* owned) {
             multGrid[tv].stifPlan.reset();  // assembled once: the plan and its device copy are not kept
             t_stif[tv] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
+    std::exception_ptr chainFailed;
 #pragma omp parallel for schedule(dynamic, 1)
     for (int64_t tv = 0; tv < nsub; ++tv) {
         if (!mine(tv)) continue;
@@ -330,17 +332,34 @@ void MCONTACT::ESTABLISH(const std::vector<uint8_t>* owned) {
             for (int s = 0; s < 2; ++s)
                 if (itf.body[s] == tv) g.ADD_NODAL(itf.systMass[s]);
         auto t3 = now();
-        g.CONSTRAINT();
+        if (galerkinBy) {
+            // an error of the device chain (DDPCA_EHIP: a failed allocation) cannot leave the
+            // OpenMP region as an exception: the first one is kept and rethrown after the loop
+            g.galerkinChain = galerkinBy;
+            try {
+                g.CONSTRAINT();
+            } catch (...) {
+#pragma omp critical(ddpca_establish_chain_failed)
+                if (!chainFailed) chainFailed = std::current_exception();
+                continue;
+            }
+        } else {
+            g.CONSTRAINT();
+        }
         // the hanging level's rows of prolOper[maxiLeve] (OUTP_SUB1, MULTIGRID.h:1279), read by the
         // device (op_hang) as for an operator-level subdomain (ddpca_problem_set_hanging)
         if (g.nodeAll) g.hangProl = g.hangRows();
         auto t4 = now();
         if (verbose) {
             auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-            std::fprintf(stderr, "[ddpca] establish sd %ld: transfer %.0f ms, stif %.0f ms, systMass %.0f ms, constraint %.0f ms\n",
-                         (long)tv, t_transfer[tv], stifValues ? t_stif[tv] : ms(t1, t2), ms(t2, t3), ms(t3, t4));
+            std::fprintf(stderr,
+                         "[ddpca] establish sd %ld: transfer %.0f ms, stif %.0f ms, systMass %.0f ms, constraint %.0f ms "
+                         "(galerkin %.0f ms%s)\n",
+                         (long)tv, t_transfer[tv], stifValues ? t_stif[tv] : ms(t1, t2), ms(t2, t3), ms(t3, t4), g.galerkinMs,
+                         galerkinBy ? ", device" : "");
         }
     }
+    if (chainFailed) std::rethrow_exception(chainFailed);
     // ---- coarse space (MCONTACT.h:858-863)
     if ((muscSett & 3) == 3)
         throw std::invalid_argument("muscSett: choose one coarse space (1 = MULTISCALE, 2 = MULTISCALE_1)");

@@ -96,6 +96,9 @@ public:
     // set (ddpca_problem_set_assembly_device): ESTABLISH assembles every owned subdomain's
     // stiffness through it, in a serial pass before the loop over subdomains (STIF_MATR_BY)
     std::function<void(MULTIGRID&, double* val)> stifValues;
+    // set (ddpca_problem_set_galerkin_device): every owned subdomain's CONSTRAINT leaves its
+    // Galerkin chain to it (MULTIGRID::galerkinChain), from ESTABLISH's loop over the subdomains
+    GalerkinChain galerkinBy;
     double GET_CHAR_LENG() const;  // MCONTACT.h:2478-2491
 };
 

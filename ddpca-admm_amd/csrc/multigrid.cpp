@@ -2,6 +2,7 @@
 #include "multigrid.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -962,8 +963,22 @@ void MULTIGRID::CONSTRAINT() {
     PROL_OPER();
     // the hanging level's Galerkin step, then the hierarchy (MULTIGRID.h:1182-1184)
     levelStif.assign(L + 1, Bsr3());
-    levelStif[L] = nodeAll ? galerkin_rap(K, prolHang) : std::move(K);
-    for (int64_t l = L - 1; l >= 0; --l) levelStif[l] = galerkin_rap(levelStif[l + 1], prolOper[l]);
+    const auto tg = std::chrono::steady_clock::now();
+    if (galerkinChain) {
+        std::vector<const Stencil*> chain;
+        if (nodeAll) chain.push_back(&prolHang);
+        for (int64_t l = L - 1; l >= 0; --l) chain.push_back(&prolOper[l]);
+        std::vector<Bsr3> out;
+        galerkinChain(K, chain, out);
+        if (out.size() != chain.size()) throw std::runtime_error("CONSTRAINT: the Galerkin hook returned the wrong number of levels");
+        size_t i = 0;
+        levelStif[L] = nodeAll ? std::move(out[i++]) : std::move(K);
+        for (int64_t l = L - 1; l >= 0; --l) levelStif[l] = std::move(out[i++]);
+    } else {
+        levelStif[L] = nodeAll ? galerkin_rap(K, prolHang) : std::move(K);
+        for (int64_t l = L - 1; l >= 0; --l) levelStif[l] = galerkin_rap(levelStif[l + 1], prolOper[l]);
+    }
+    galerkinMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tg).count();
     FLAGS();
     // consForc = consOper (prolOper[maxiLeve]^T f - K_L d), loads not rotated, d the prescribed
     // values of the fine level's constrained dofs (MULTIGRID.h:1186-1243)

@@ -84,6 +84,8 @@ struct StifColours {
     std::vector<std::vector<int64_t>> list;
 };
 
+using GalerkinChain = std::function<void(const Bsr3& K, const std::vector<const Stencil*>& chain, std::vector<Bsr3>& out)>;
+
 class MULTIGRID {
 public:
     // ---------------------------------------------------------------- mesh
@@ -188,6 +190,12 @@ public:
     void PROL_OPER();   // prolOper / prolHang from the stencils and nodeRota (CONSTRAINT's first step;
                         // the coarse spaces read it on subdomains this rank does not build)
     void CONSTRAINT();  // FLAGS + Galerkin hierarchy + condensed load
+    // the Galerkin chain of CONSTRAINT (MULTIGRID.h:1182-1184) left to this hook when set (the
+    // device products, device_galerkin.hip): the finest operator (R^T K R done) and the stencils,
+    // prolHang first when there is a hanging level, then prolOper[maxiLeve - 1] ... prolOper[0];
+    // out[i] = chain[i]^T (out[i - 1], or K for i = 0) chain[i].  Empty: galerkin_rap on the host.
+    GalerkinChain galerkinChain;
+    double galerkinMs = 0.0;  // host clock of the chain in the last CONSTRAINT (DDPCA_VERBOSE)
 
     // ---------------------------------------------------------------- per-iteration adapters
     // f_free = consOper * prolOper^T * earlTran^T * f_nodal (identities except consOper here)

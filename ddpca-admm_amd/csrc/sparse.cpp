@@ -195,6 +195,62 @@ Bsr3 galerkin_rap(const Bsr3& A, const Stencil& S) {
     return C;
 }
 
+GalerkinPattern galerkin_pattern(const Bsr3& A, const Stencil& S) {
+    const int64_t nc = S.nc;
+    GalerkinPattern G;
+    G.nc = nc;
+    // S^T as galerkin_rap builds it: coarse node -> (fine node ascending, entry index)
+    G.tptr.assign(nc + 1, 0);
+    for (int64_t f = 0; f < S.nf; ++f)
+        for (int64_t k = S.ptr[f]; k < S.ptr[f + 1]; ++k) G.tptr[S.col[k] + 1]++;
+    for (int64_t c = 0; c < nc; ++c) G.tptr[c + 1] += G.tptr[c];
+    G.tfine.resize(G.tptr[nc]);
+    G.tent.resize(G.tptr[nc]);
+    {
+        std::vector<int64_t> fill(G.tptr.begin(), G.tptr.end() - 1);
+        for (int64_t f = 0; f < S.nf; ++f)
+            for (int64_t k = S.ptr[f]; k < S.ptr[f + 1]; ++k) {
+                const int64_t p = fill[S.col[k]]++;
+                G.tfine[p] = (int32_t)f;
+                G.tent[p] = k;
+            }
+    }
+    // the boolean pass over galerkin_rap's traversal, twice: the row lengths, then the columns;
+    // mark[c2] == c1 while coarse column c2 is already in row c1 (fresh marks in each pass)
+    G.ptr.assign(nc + 1, 0);
+    for (int fill = 0; fill < 2; ++fill) {
+#pragma omp parallel
+        {
+            std::vector<int64_t> mark(nc, -1);
+#pragma omp for schedule(dynamic, 64)
+            for (int64_t c1 = 0; c1 < nc; ++c1) {
+                int64_t n = 0;
+                int32_t* out = fill ? G.col.data() + G.ptr[c1] : nullptr;
+                for (int64_t t = G.tptr[c1]; t < G.tptr[c1 + 1]; ++t) {
+                    const int64_t f1 = G.tfine[t];
+                    for (int64_t k = A.ptr[f1]; k < A.ptr[f1 + 1]; ++k) {
+                        const int64_t f2 = A.col[k];
+                        for (int64_t s = S.ptr[f2]; s < S.ptr[f2 + 1]; ++s) {
+                            const int32_t c2 = S.col[s];
+                            if (mark[c2] == c1) continue;
+                            mark[c2] = c1;
+                            if (fill) out[n] = c2;
+                            ++n;
+                        }
+                    }
+                }
+                if (fill) std::sort(out, out + n);
+                else G.ptr[c1 + 1] = n;
+            }
+        }
+        if (!fill) {
+            for (int64_t c = 0; c < nc; ++c) G.ptr[c + 1] += G.ptr[c];
+            G.col.resize(G.ptr[nc]);
+        }
+    }
+    return G;
+}
+
 Csr condense(const Bsr3& A, const std::vector<int32_t>& free_index, int64_t nfree) {
     Csr C;
     C.nrow = C.ncol = nfree;

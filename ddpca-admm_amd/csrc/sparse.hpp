@@ -52,6 +52,22 @@ struct Stencil {
 // MULTIGRID.h:1182-1184), S's block entries (rotated nodes) taken as their 3x3 blocks.
 Bsr3 galerkin_rap(const Bsr3& A, const Stencil& S);
 
+// The structure of S^T A S alone, exactly as galerkin_rap stores it: every coarse column a triple
+// (f1 -> c1, block (f1, f2) of A, f2 -> c2) touches, also where the values cancel; columns
+// ascending within a row; an empty row for a coarse node no entry names.  Beside it S^T: the
+// entries of coarse node c are [tptr[c], tptr[c + 1]), fine nodes ascending (tfine) with their
+// entry index into S.col / S.w (tent): the order in which galerkin_rap adds a row's terms.  What
+// the device product (device_galerkin.hip) runs on.
+struct GalerkinPattern {
+    int64_t nc = 0;
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> col;
+    std::vector<int64_t> tptr;
+    std::vector<int32_t> tfine;
+    std::vector<int64_t> tent;
+};
+GalerkinPattern galerkin_pattern(const Bsr3& A, const Stencil& S);
+
 // Expand to scalar CSR keeping only dofs with keep[dof] != 0 (consOper * A * consOper^T,
 // MULTIGRID.h:1213-1227).  free_index[dof] = condensed index or -1.
 Csr condense(const Bsr3& A, const std::vector<int32_t>& free_index, int64_t nfree);

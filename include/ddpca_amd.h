@@ -428,6 +428,47 @@ int ddpca_problem_set_assembly_device(ddpca_problem_t p, int device);
  * clock in ms of the plan build, its upload (both 0 once cached) and the copy back of the values. */
 int ddpca_stif_last_kernel_ms(double* out2);
 int ddpca_stif_last_host_ms(double* out3);
+/* The Galerkin product of MULTIGRID::CONSTRAINT (MULTIGRID.h:1182-1184), C = P^T A P, on operands
+ * of the caller: A as BSR3 on nf nodes (a_ptr[nf + 1], a_col, a_val 9 doubles per block, row-major)
+ * and P = S (x) I3 given by the node stencil S (nf x nc: s_ptr[nf + 1], s_col, s_w), nbent of whose
+ * entries (bent: indices into s_col, strictly ascending; bval: 9 doubles each, row-major) are full
+ * 3x3 blocks in place of w I (rotated nodes; nbent = 0: bent / bval may be NULL).  The handle holds
+ * C as BSR3 on nc nodes: every coarse column a triple touches is stored, also where the values
+ * cancel, columns ascending, an empty row for a coarse node no entry names.  device < 0: the
+ * host's galerkin_rap; device >= 0: the pattern on the host (galerkin_pattern) and the values by
+ * the fp64 kernel k_rap on that GPU, in the host's summation order without atomics, so two calls
+ * return the same bits; a failed device allocation is DDPCA_EHIP and the message names the size;
+ * there is no host fallback.  DDPCA_EINVAL: a NULL argument, negative nf / nc, a ptr that does not
+ * start at 0 or decreases, a column of A outside [0, nf), a column of S outside [0, nc), bent out
+ * of range or not ascending. */
+typedef struct ddpca_galerkin* ddpca_galerkin_t;
+int ddpca_galerkin_rap(int device, int64_t nf, int64_t nc, const int64_t* a_ptr, const int32_t* a_col, const double* a_val,
+                       const int64_t* s_ptr, const int32_t* s_col, const double* s_w, int64_t nbent, const int64_t* bent,
+                       const double* bval, ddpca_galerkin_t* out);
+/* MULTIGRID.h:1182-1184: the product held by the handle, *nb block rows; owned by the handle. */
+int ddpca_galerkin_view(ddpca_galerkin_t h, const int64_t** ptr, const int32_t** col, const double** val, int64_t* nb);
+/* MULTIGRID.h:1182-1184: frees the product. */
+int ddpca_galerkin_destroy(ddpca_galerkin_t h);
+/* ddpca_multigrid_build (MULTIGRID.h:722-1255) with either part on a GPU: assembly_device >= 0 as
+ * ddpca_multigrid_build_on; galerkin_device >= 0: the Galerkin chain of CONSTRAINT(1)
+ * (MULTIGRID.h:1182-1184: the hanging level's step, then every level down to 0) by k_rap on that
+ * GPU, one product after the other without a host round trip of the values between them, the
+ * rotation R^T K R, the dof flags and the condensed load on the host as before.  Both < 0 is
+ * ddpca_multigrid_build. */
+int ddpca_multigrid_build_with(ddpca_multigrid_t g, const ddpca_csr_t* extra, int assembly_device, int galerkin_device);
+/* Before ddpca_problem_establish(_owned): the Galerkin chain (MULTIGRID.h:1182-1184) of every owned
+ * subdomain's CONSTRAINT(1) in MCONTACT::ESTABLISH on GPU `device`; the host threads of the loop
+ * over the subdomains take the GPU one chain at a time.  device < 0 (the default): galerkin_rap on
+ * the host.  DDPCA_ESTATE once the problem is established. */
+int ddpca_problem_set_galerkin_device(ddpca_problem_t p, int device);
+/* Measurement only (profiles/galerkin_probe.py; no reference counterpart; the chain of
+ * MULTIGRID.h:1182-1184), of the calling thread's last device chain or device ddpca_galerkin_rap:
+ * host clock in ms of the pattern build and of the uploads, HIP-event time of the kernels summed
+ * over the levels, host clock of the copies back (with the sizing of the host arrays they fill).
+ * ddpca_galerkin_last_level_ms: the kernel time
+ * of each product of that chain in its order, at most cap of them; returns their number. */
+int ddpca_galerkin_last_ms(double* out4);
+int ddpca_galerkin_last_level_ms(double* out, int64_t cap);
 /* The whole MCONTACT::ESTABLISH (MCONTACT.h:181-896) from element trees: subdomain tv of an empty
  * problem (ddpca_problem_empty) takes a copy of the UNBUILT multigrid g (its tree and the inputs
  * set with ddpca_multigrid_set: constraints, loads, rotations, coupled nodes, material);
