@@ -148,6 +148,7 @@ def _declare(L: C.CDLL) -> None:
                                      C.POINTER(C.c_int)]
     L.ddpca_problem_destroy.argtypes = [_P]
     L.ddpca_problem_mgpis.argtypes = [_P, C.c_int64, C.c_int, C.POINTER(MgpisOptions), C.POINTER(_P)]
+    L.ddpca_problem_mgpis_batch.argtypes = [_P, C.c_int64, _P, C.c_int, C.POINTER(MgpisOptions), C.c_int, C.POINTER(_P)]
     L.ddpca_problem_empty.argtypes = [C.c_int64, C.c_int64, C.POINTER(_P)]
     L.ddpca_problem_set_contact.argtypes = [_P, C.c_int64, C.c_int64, C.c_int64]
     L.ddpca_problem_set_subdomain_tree.argtypes = [_P, C.c_int64, _P]
@@ -204,6 +205,8 @@ def _declare(L: C.CDLL) -> None:
     L.ddpca_galerkin_last_ms.argtypes = [_DP]
     L.ddpca_galerkin_last_level_ms.argtypes = [_DP, C.c_int64]
     L.mgpis_gpu_vcycle.argtypes = [_P, _P, _P]
+    L.mgpis_gpu_batch_vcycle.argtypes = [_P, _P, _P, _P]
+    L.mgpis_gpu_batch_solve.argtypes = [_P, _P, _P, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P]
     L.mgpis_gpu_info.argtypes = [_P, _I64P]
     L.mgpis_gpu_vcycle_info.argtypes = [_P, C.c_char_p, C.c_int, _P, C.c_int64]
     L.mgpis_gpu_vcycle_info.restype = C.c_int64
@@ -773,6 +776,16 @@ class MGPIS:
         return cls(h)
 
     @classmethod
+    def batch_from_problem(cls, problem: Problem, tvs: Sequence[int], parts: int = 0, device: int = 0, **opts) -> "MGPIS":
+        """One batched handle over the subdomains tvs, in that order, as MCONTACT builds its body-balance
+        batch (ddpca_problem_mgpis_batch; parity tests).  parts: 0 one stream, 2..4 a split batch."""
+        h = C.c_void_p()
+        o = default_options(**opts)
+        tv = np.ascontiguousarray(tvs, dtype=np.int64)
+        _check(lib().ddpca_problem_mgpis_batch(problem.handle, len(tv), _ptr(tv), device, C.byref(o), int(parts), C.byref(h)))
+        return cls(h)
+
+    @classmethod
     def from_csr(cls, nnodes: Sequence[int], free_dof: Sequence[np.ndarray], K: Sequence, S: Sequence,
                  device: int = 0, **opts) -> "MGPIS":
         """Reference layout: consStif[l] (scipy CSR, condensed), free_dof[l], scalar stencils S[l]."""
@@ -847,12 +860,13 @@ class MGPIS:
         member) and "coef" (doubles, (c1, c2) per sweep and member) of a level >= 1 (default: the fine
         one), "colour" (int32 per fine node in the reference numbering, -1 = not colour-swept),
         "levels" (int32, nlev x [exact level, lattice transfers, rotation block entries, fp32 iterate
-        copy, V-cycle copy's storage type])."""
+        copy, V-cycle copy's storage type]), "part" (int32 per member: its part of a split batch, -1 when
+        not split), "nfree" (int64 per member: its condensed fine-level dofs)."""
         lev = self.info()["nlev"] - 1 if level is None else int(level)
         n = lib().mgpis_gpu_vcycle_info(self._h, what.encode(), lev, None, 0)
         if n < 0:
             _check(int(n))
-        out = np.zeros(n, dtype=np.float64 if what in ("lmax", "coef") else np.int32)
+        out = np.zeros(n, dtype=np.float64 if what in ("lmax", "coef") else np.int64 if what == "nfree" else np.int32)
         if n:
             m = lib().mgpis_gpu_vcycle_info(self._h, what.encode(), lev, _ptr(out), n)
             if m < 0:
@@ -908,6 +922,50 @@ class MGPIS:
         z = np.zeros_like(r)
         _check(lib().mgpis_gpu_vcycle(self._h, _ptr(r), _ptr(z)))
         return z
+
+    def _members(self, vs: Sequence[np.ndarray], what: str) -> tuple:
+        """(the members' vectors concatenated, the split points) after checking them against vcycle_info("nfree")"""
+        nf = self.vcycle_info("nfree")
+        if len(vs) != len(nf) or any(np.shape(v) != (n,) for v, n in zip(vs, nf)):
+            raise ValueError(f"{what}: one vector of nfree = {list(nf)} entries per member")
+        return np.concatenate([np.asarray(v, dtype=np.float64) for v in vs]), np.cumsum(nf)[:-1]
+
+    def MULT_VCYC_batch(self, rs: Sequence[np.ndarray], done: Optional[Sequence[int]] = None,
+                        z0: Optional[Sequence[np.ndarray]] = None) -> list:
+        """z = M^-1 r on every member of the batch at once (mgpis_gpu_batch_vcycle) -> per-member list.
+        done: per member, nonzero = marked done before the cycle, so its z comes back as z0's (default
+        zeros) bits."""
+        r, cut = self._members(rs, "rs")
+        z = np.zeros_like(r) if z0 is None else self._members(z0, "z0")[0].copy()
+        d = None if done is None else np.ascontiguousarray(done, dtype=np.int32)
+        if d is not None and len(d) != len(rs):
+            raise ValueError("done: one flag per member")
+        _check(lib().mgpis_gpu_batch_vcycle(self._h, _ptr(r), _ptr(z), None if d is None else _ptr(d)))
+        return np.split(z, cut)
+
+    def CG_SOLV_batch(self, precSwit: int, bs: Sequence[np.ndarray], rtol: float = 1e-14,
+                      maxit: Optional[Sequence[int]] = None, warm: bool = False,
+                      x0: Optional[Sequence[np.ndarray]] = None) -> tuple:
+        """One batched PCG over every member (mgpis_gpu_batch_solve) -> (x per member, iterations,
+        recursive relative residuals, fail flags); maxit per member (default: its rows).  warm: start
+        from x0.  A breakdown raises DdpcaError(DDPCA_ENUMERIC) with the same tuple as its .partial."""
+        b, cut = self._members(bs, "bs")
+        n = len(bs)
+        if warm and x0 is None:
+            raise ValueError("warm: x0 per member")
+        x = self._members(x0, "x0")[0].copy() if warm else np.zeros_like(b)
+        mi = np.ascontiguousarray([len(v) for v in bs] if maxit is None else maxit, dtype=np.int64)
+        if len(mi) != n:
+            raise ValueError("maxit: one cap per member")
+        it, rr, fl = np.zeros(n, np.int64), np.zeros(n), np.zeros(n, np.int32)
+        rc = lib().mgpis_gpu_batch_solve(self._h, _ptr(b), _ptr(x), precSwit, rtol, _ptr(mi), 1 if warm else 0,
+                                         _ptr(it), _ptr(rr), _ptr(fl))
+        out = (np.split(x, cut), it, rr, fl)
+        if rc < 0:
+            e = DdpcaError(rc, lib().ddpca_last_error().decode())
+            e.partial = out
+            raise e
+        return out
 
     def spmv(self, x: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(x, dtype=np.float64)

@@ -11,6 +11,7 @@
 #include "../../include/ddpca_amd.h"
 #include "device_mgpis.hpp"
 #include "problem.hpp"
+#include "subdomain_ops.hpp"
 
 using namespace ddpca;
 
@@ -27,24 +28,67 @@ mgpis_options_t resolve(const mgpis_options_t* opt) {
     return o;
 }
 
+// The reference calls CG_SOLV on different MGPIS objects from an omp parallel for
+// (MCONTACT.h:2511-2531): every graph a solve replays is captured here, on the creating
+// thread, so a solve only replays (no capture on a solving thread), and the
+// solve's condensed staging buffer is allocated here too (no hipMalloc / hipFree per solve).
+std::unique_ptr<MgpisDevice> finish_create(std::unique_ptr<MgpisDevice> d) {
+    d->prepare_graphs(0);
+    if (!d->no_coarse) d->prepare_graphs(1);
+    int64_t n = 0;
+    for (int64_t f : d->nfree) n += f;
+    d->stage.alloc((size_t)std::max<int64_t>(n, 1));
+    return d;
+}
+
 std::unique_ptr<MgpisDevice> single(int device, const std::vector<int64_t>& nn, const std::vector<const Bsr3*>& B,
                                     const std::vector<uint8_t>& fr, const std::vector<const Stencil*>& S,
-                                    const mgpis_options_t* opt, const double* coords = nullptr) {
+                                    const mgpis_options_t* opt) {
     SubdomainOps ops;
     ops.nnodes = nn;
     ops.K = B;
     ops.dof_free = fr.data();
     ops.S = S;
-    ops.coords = coords;
-    auto d = std::make_unique<MgpisDevice>(device, std::vector<SubdomainOps>{ops}, resolve(opt));
-    // The reference calls CG_SOLV on different MGPIS objects from an omp parallel for
-    // (MCONTACT.h:2511-2531): every graph a solve replays is captured here, on the creating
-    // thread, so a solve only replays (no capture on a solving thread), and the
-    // solve's condensed staging buffer is allocated here too (no hipMalloc / hipFree per solve).
-    d->prepare_graphs(0);
-    if (!d->no_coarse) d->prepare_graphs(1);
-    d->stage.alloc((size_t)std::max<int64_t>(d->nfree[0], 1));
-    return d;
+    return finish_create(std::make_unique<MgpisDevice>(device, std::vector<SubdomainOps>{ops}, resolve(opt)));
+}
+
+// One MgpisDevice over the listed subdomains of an established problem, in the listed order
+// (subdomain_ops: what the MCONTACT batch is built from); parts >= 2: set_split before the capture.
+std::unique_ptr<MgpisDevice> from_problem(ddpca_problem_t p, int64_t ntv, const int64_t* tv, int device,
+                                          const mgpis_options_t* opt, int parts) {
+    if (!p || !tv || ntv < 1) throw ApiError(DDPCA_EINVAL, "null argument");
+    Problem& P = *reinterpret_cast<Problem*>(p);
+    if (!P.established) throw ApiError(DDPCA_ESTATE, "problem not established");
+    if (parts != 0 && (parts < 2 || parts > kMaxParts)) throw ApiError(DDPCA_EINVAL, "parts must be 0 or 2 .. 4");
+    std::vector<SubdomainOps> ops;
+    for (int64_t i = 0; i < ntv; ++i) {
+        if (tv[i] < 0 || tv[i] >= (int64_t)P.mc.multGrid.size()) throw ApiError(DDPCA_EINVAL, "subdomain index");
+        if (!P.owned.empty() && !P.owned[tv[i]])
+            throw ApiError(DDPCA_ESTATE, "subdomain " + std::to_string(tv[i]) + " was not established");
+        ops.push_back(subdomain_ops(P.mc.multGrid[tv[i]]));
+    }
+    auto d = std::make_unique<MgpisDevice>(device, ops, resolve(opt));
+    if (parts >= 2) d->set_split(true, parts);
+    return finish_create(std::move(d));
+}
+
+// first condensed entry of every member in the batch vectors (nsub + 1)
+std::vector<int64_t> member_offsets(const MgpisDevice& D) {
+    std::vector<int64_t> off(D.nsub + 1, 0);
+    for (int s = 0; s < D.nsub; ++s) off[s + 1] = off[s] + D.nfree[s];
+    return off;
+}
+
+// condensed host vector (member after member) -> the fine level's batch nodal layout, through stage
+void upload_members(MgpisDevice& D, const std::vector<int64_t>& off, const double* host, double* full) {
+    DDPCA_HIP(hipMemcpyAsync(D.stage.p, host, off[D.nsub] * sizeof(double), hipMemcpyHostToDevice, D.stream));
+    for (int s = 0; s < D.nsub; ++s) D.scatter_free(s, D.stage.p + off[s], full);
+}
+
+void download_members(MgpisDevice& D, const std::vector<int64_t>& off, const double* full, double* host) {
+    for (int s = 0; s < D.nsub; ++s) D.gather_free(s, full, D.stage.p + off[s]);
+    DDPCA_HIP(hipMemcpyAsync(host, D.stage.p, off[D.nsub] * sizeof(double), hipMemcpyDeviceToHost, D.stream));
+    DDPCA_HIP(hipStreamSynchronize(D.stream));
 }
 
 }  // namespace
@@ -156,20 +200,15 @@ int mgpis_gpu_create_bsr3(int device, int nlev, const int64_t* nnodes, const int
 }
 
 int ddpca_problem_mgpis(ddpca_problem_t p, int64_t tv, int device, const mgpis_options_t* opt, mgpis_t* out) {
+    return ddpca_problem_mgpis_batch(p, 1, &tv, device, opt, 0, out);
+}
+
+int ddpca_problem_mgpis_batch(ddpca_problem_t p, int64_t ntv, const int64_t* tv, int device, const mgpis_options_t* opt,
+                              int parts, mgpis_t* out) {
     return guarded([&] {
-        Problem& P = *reinterpret_cast<Problem*>(p);
-        if (!P.established) throw ApiError(DDPCA_ESTATE, "problem not established");
-        if (tv < 0 || tv >= (int64_t)P.mc.multGrid.size()) throw ApiError(DDPCA_EINVAL, "subdomain index");
-        const MULTIGRID& g = P.mc.multGrid[tv];
-        std::vector<int64_t> nn(g.leveCount.begin(), g.leveCount.end());
-        std::vector<const Bsr3*> Bp;
-        std::vector<const Stencil*> Sp;
-        for (const auto& b : g.levelStif) Bp.push_back(&b);
-        // prolOper: scalProl with the nodal rotations' 3x3 blocks as block entries (== scalProl without
-        // nodeRota), as the MCONTACT batch takes it; an operator-level subdomain has scalProl only
-        for (const auto& s : g.prolOper.empty() ? g.scalProl : g.prolOper) Sp.push_back(&s);
+        if (!out) throw ApiError(DDPCA_EINVAL, "null argument");
         auto h = std::make_unique<ddpca_mgpis>();
-        h->dev = single(device, nn, Bp, g.consFlag, Sp, opt, g.nodeCoor.empty() ? nullptr : g.nodeCoor[0].data());
+        h->dev = from_problem(p, ntv, tv, device, opt, parts);
         *out = h.release();
     });
 }
@@ -285,6 +324,49 @@ int mgpis_gpu_vcycle(mgpis_t h, const double* r, double* z) {
     });
 }
 
+int mgpis_gpu_batch_vcycle(mgpis_t h, const double* r, double* z, const int32_t* done) {
+    return guarded([&] {
+        if (!h || !r || !z) throw ApiError(DDPCA_EINVAL, "null argument");
+        MgpisDevice& D = *h->dev;
+        select_device(D.device);
+        if (D.no_coarse) throw ApiError(DDPCA_ESTATE, "one-level handle without a coarse inverse: no V-cycle");
+        const std::vector<int64_t> off = member_offsets(D);
+        upload_members(D, off, r, D.rs.p);
+        upload_members(D, off, z, D.zs.p);
+        std::vector<PcgScal> sc(D.nsub, PcgScal{});
+        for (int s = 0; s < D.nsub; ++s) sc[s].done = done && done[s] ? 1 : 0;
+        DDPCA_HIP(hipMemcpyAsync(D.sc.p, sc.data(), D.nsub * sizeof(PcgScal), hipMemcpyHostToDevice, D.stream));
+        D.vcycle(D.rs.p, D.zs.p, false);
+        download_members(D, off, D.zs.p, z);
+    });
+}
+
+int mgpis_gpu_batch_solve(mgpis_t h, const double* b, double* x, int prec, double rtol, const int64_t* maxit, int warm,
+                          int64_t* iters, double* relres, int32_t* fail) {
+    return guarded([&] {
+        if (!h || !b || !x || !maxit) throw ApiError(DDPCA_EINVAL, "null argument");
+        if (prec != 0 && prec != 1) throw ApiError(DDPCA_EINVAL, "prec must be 0 or 1");
+        MgpisDevice& D = *h->dev;
+        select_device(D.device);
+        if (prec == 1 && D.no_coarse) throw ApiError(DDPCA_ESTATE, "one-level handle without a coarse inverse: diagonal preconditioner only");
+        const std::vector<int64_t> off = member_offsets(D);
+        upload_members(D, off, b, D.bs.p);
+        if (warm) upload_members(D, off, x, D.xs.p);
+        D.pcg_begin(prec, rtol, std::vector<int64_t>(maxit, maxit + D.nsub), warm != 0);
+        D.pcg_wait(prec, 0);
+        D.pcg_fetch();
+        DDPCA_HIP(hipStreamSynchronize(D.stream));
+        for (int s = 0; s < D.nsub; ++s) {
+            const PcgScal& c = D.sc_host[s];
+            if (iters) iters[s] = c.iter;
+            if (relres) relres[s] = c.bb > 0 ? std::sqrt(c.rr / c.bb) : 0.0;
+            if (fail) fail[s] = c.fail;
+        }
+        download_members(D, off, D.xs.p, x);
+        D.pcg_check();  // a breakdown throws DDPCA_ENUMERIC here, the outputs above already filled
+    });
+}
+
 int mgpis_gpu_info(mgpis_t h, int64_t* out7) {
     return guarded([&] {
         MgpisDevice& D = *h->dev;
@@ -346,6 +428,12 @@ int64_t mgpis_gpu_vcycle_info(mgpis_t h, const char* what, int level, void* out,
                 for (int e : {D.clev, (int)L.lat, (int)(L.nrot != 0), (int)x4, D.vc_type(l)}) v.push_back(e);
             }
             put(v);
+        } else if (w == "part") {
+            std::vector<int32_t> v;
+            for (int s = 0; s < D.nsub; ++s) v.push_back(D.part_of(s));
+            put(v);
+        } else if (w == "nfree") {
+            put(D.nfree);
         } else {
             throw ApiError(DDPCA_EINVAL, "vcycle_info: unknown item");
         }

@@ -48,6 +48,7 @@
 #include "device_mgpis.hpp"
 #include "device_stress.hpp"
 #include "problem.hpp"
+#include "subdomain_ops.hpp"
 
 using namespace ddpca;
 
@@ -1751,16 +1752,7 @@ void build(ddpca_mcontact& H, Problem& P) {
         if (P.owned.size() != (size_t)H.nsub || !P.owned[tv])
             throw ApiError(DDPCA_ESTATE, "subdomain " + std::to_string(tv) + " is owned by this rank but was not established");
         const MULTIGRID& g = mc.multGrid[tv];
-        SubdomainOps o;
-        o.nnodes.assign(g.leveCount.begin(), g.leveCount.end());
-        for (const auto& b : g.levelStif) o.K.push_back(&b);
-        // prolOper: scalProl with the nodal rotations' 3x3 blocks as block entries (MULTIGRID.h:
-        // 1141-1181; == scalProl without nodeRota); an operator-level subdomain has scalProl only
-        // (its block entries already in it)
-        for (const auto& s : g.prolOper.empty() ? g.scalProl : g.prolOper) o.S.push_back(&s);
-        o.dof_free = g.consFlag.data();
-        o.coords = g.nodeCoor.empty() ? nullptr : g.nodeCoor[0].data();
-        ops.push_back(o);
+        ops.push_back(subdomain_ops(g));
         ddpca_mcontact::Sub S;
         S.tv = tv;
         S.nn = g.leveCount.back();

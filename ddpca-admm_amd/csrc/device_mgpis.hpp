@@ -321,6 +321,7 @@ public:
     // parts > 2 (DDPCA_PCG_STREAMS=n): the same with n parts on n streams (A/B)
     void set_split(bool on, int parts = 2);
     bool split() const { return split_; }
+    int part_of(int s) const { return split_ ? half_host_[s] : -1; }  // member s's part, -1 when not split
     // capture the PCG graphs of preconditioner prec now (create time) instead of at the first solve
     void prepare_graphs(int prec) { build_graph(prec); }
 

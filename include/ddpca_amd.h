@@ -184,8 +184,27 @@ int mgpis_gpu_info(mgpis_t h, int64_t* out7);
  *             when the lattice transfer form was accepted into this level, 1 when the transfer into
  *             it carries rotation block entries, 1 when its iterate lives in an fp32 copy, the storage
  *             type of its V-cycle copy (0 fp64, 1 fp32, 2 block-exponent fp16, 3 block-scaled int8)
- *             (level is ignored) */
+ *             (level is ignored)
+ *   "part"    int32 per member: the part of the split batch whose graphs run it (set_split), -1 on
+ *             a handle that is not split (level is ignored)
+ *   "nfree"   int64 per member: its condensed fine-level dofs, the member's share of the batch
+ *             vectors of mgpis_gpu_batch_vcycle / mgpis_gpu_batch_solve (level is ignored) */
 int64_t mgpis_gpu_vcycle_info(mgpis_t h, const char* what, int level, void* out, int64_t cap);
+/* The batched handle's V-cycle and PCG, member by member (no reference counterpart), for parity tests
+ * of the path MCONTACT's body balance runs (tests/test_batch_parity_gpu.py).  h: any handle, usually
+ * one of ddpca_problem_mgpis_batch; vectors are condensed, member after member (sum of "nfree").
+ * mgpis_gpu_batch_vcycle: z = M^-1 r on every member in one launch sequence.  z is in/out: it is
+ * uploaded into the fine output vector before the cycle, and done[s] != 0 marks member s done
+ * (PcgScal::done) before it, so that member's chunks exit at once and its z comes back with the
+ * caller's bits.  done == NULL: nobody is done. */
+int mgpis_gpu_batch_vcycle(mgpis_t h, const double* r, double* z, const int32_t* done);
+/* One pcg_begin / pcg_wait / pcg_finish over the batch, as MCONTACT's body balance runs it: maxit[s]
+ * per member (<= 0: done at init, x = 0), warm != 0: x carries x0.  Fills iters[s], relres[s] (the
+ * recursive ||r|| / ||b||) and fail[s] (any may be NULL).  A breakdown in a member returns
+ * DDPCA_ENUMERIC naming it, with iters / relres / fail / x filled all the same; the handle stays
+ * usable.  Returns 0 otherwise (a member stopped by its cap is not reported). */
+int mgpis_gpu_batch_solve(mgpis_t h, const double* b, double* x, int prec, double rtol, const int64_t* maxit, int warm,
+                          int64_t* iters, double* relres, int32_t* fail);
 /* Diagnostic (no reference counterpart): average ms per launch of a fine-level SELL-BSR3
  * kernel over `reps` back-to-back launches on this operator.  variant = loop (0 cached x3
  * unroll, 1 non-temporal matrix loads, 2 column prefetch + non-temporal, 3 a bound only: x
@@ -274,6 +293,13 @@ int ddpca_problem_destroy(ddpca_problem_t p);
 /* Build the device solver of subdomain tv from the problem (mgpis_gpu_create_bsr3). */
 int ddpca_problem_mgpis(ddpca_problem_t p, int64_t tv, int device, const mgpis_options_t* opt,
                         mgpis_t* out);
+/* One batched device solver over the subdomains tv[0 .. ntv) of an established problem, in the listed
+ * order, built from the same per-subdomain operators as MCONTACT's body-balance batch (no reference
+ * counterpart; for the parity tests of the batched path, mgpis_gpu_batch_vcycle / _solve).  parts: 0 =
+ * one stream, 2 .. 4 = the batch split into that many parts on streams of their own (at most one
+ * part per member).  Graphs are captured here.  ntv = 1, parts = 0 is ddpca_problem_mgpis. */
+int ddpca_problem_mgpis_batch(ddpca_problem_t p, int64_t ntv, const int64_t* tv, int device,
+                              const mgpis_options_t* opt, int parts, mgpis_t* out);
 
 /* ---- Operator-level builder: a caller that already holds the reference's operators (its
  * MULTIGRID/MGPIS hierarchy per subdomain and the interface operators of MCONTACT::ESTABLISH,

@@ -16,7 +16,10 @@ host here (vcycle_host.host_args); the parity test reads the device's own.
     c4  CSR drop-in on beam_s2                                            5.2e-12
         realProl drop-in on the rotated beam_s1 hierarchy                 7.1e-14
     c5  headline gl 2, precond_fp32 1-3, smoothers 1 / 3 / 4              2.2e-16 .. 3.8e-16
-  so the parity tolerance max(1e-13, 50 x floor) is 1e-13 everywhere but on the slender beams of c4
+    u   uneven chain, members 5 / 0 / 2 / 7 (test_batch_parity_gpu.py), its five right-hand sides,
+        exact level 0 / 1: fp64 storage, smoothers 0-3                    1.9e-16 .. 7.1e-16
+        precond_fp32 1 / 3, smoothers 1 / 3 / 4                           1.6e-16 .. 4.5e-16
+  (test_uneven_chain_floors), so the parity tolerance max(1e-13, 50 x floor) is 1e-13 everywhere but on the slender beams of c4
   (2.6e-10 and 3.6e-12 with the host's own lambda_max and colours; 1.3e-10 and 2.4e-12 .. 5e-12 with the
   device's), under the caps (1e-9; reduced storage 1e-6).
   The reduced-storage floor: moving EVERY fp32 inverse entry by one ulp moves a unit impulse's z by
@@ -34,6 +37,7 @@ import pytest
 
 import vcycle_host as V
 from conftest import CASE_PARAMS, golden, ref_csr
+from test_batch_parity_gpu import KINDS, U_MEMBERS, U_SETS, options as batch_options
 
 
 @pytest.mark.parametrize("case", ["beam_s1", "beam_s2", "beam_gl1"])
@@ -91,3 +95,17 @@ def test_every_mutation_is_exercised(ddpca):
                            ("swap_colours", 3)):
         o = dict(smoother=smoother, nu=2, omega=-1.7, coarse_level=0, precond_fp32=0, table_mode=0)
         assert V.VCycleHost(**V.host_args(m, o), mutate=name).mutated, name
+
+
+@pytest.mark.parametrize("st", U_SETS, ids=lambda s: f"s{s[0]}-nu{s[1]}-f{s[2]}")
+@pytest.mark.parametrize("tv", U_MEMBERS)
+def test_uneven_chain_floors(ddpca, tv, st):
+    """the members of test_batch_parity_gpu.py's batch on the uneven chain, its option sets and its
+    right-hand sides: the floor leaves the parity tolerance under its cap"""
+    m = V.load_mesh(ddpca, "u", tv)
+    rhs = {k: m["rhs"][k] for k in KINDS}
+    for cl in (0, 1):
+        o = batch_options(*st, coarse_level=cl)
+        floor, tol = V.case_tolerance(dict(mesh="u", opts=o), V.host_args(m, o), rhs)  # (asserts the cap)
+        print(f"u tv{tv} {st} cl{cl}: floor {floor:.3g} tolerance {tol:.3g}")
+        assert tol <= (1e-6 if st[2] else 1e-9)

@@ -22,8 +22,9 @@ storage, smoothers 0-3 x nu x omega x exact level 0 / L-1 / -1; c2 gl 3, smoothe
 drop-in on beam_s2 and the realProl drop-in on the rotated beam_s1 hierarchy; c5 precond_fp32 1-3 with
 smoothers 1 / 3 and colour SSOR at 1 (precond_fp32 = 4 stays pinned to 3 by test_mgpis_gpu.py).
 
-Not covered: the batched V-cycle -- several members per handle as MCONTACT builds it, per-member
-coefficients and done-member skipping -- is not reachable through mgpis_gpu_vcycle.
+The batched V-cycle -- several members per handle as MCONTACT builds it, per-member coefficients and
+done-member skipping -- and the batched PCG are held to the same restatement, member by member, in
+test_batch_parity_gpu.py (mgpis_gpu_batch_vcycle / mgpis_gpu_batch_solve).
 
 Measured device errors (MI355X, relative max-norm, every right-hand side): c1 6e-18 .. 1.1e-15, c2
 1.4e-17 .. 9.9e-16, c3 2.5e-17 .. 1.2e-15, c5 2.1e-17 .. 7.6e-16 (tolerance 1e-13); c4 CSR beam_s2 4.5e-12 ..

@@ -436,10 +436,10 @@ class VCycleHost:
         return self.apply(self.L, np.asarray(r, dtype=np.float64))
 
 
-def pcg_steps(K, b, M, k):
-    """k steps of the preconditioned CG recurrence from x0 = 0 (MGPIS::CG_SOLV, no stop rule)"""
-    x = np.zeros_like(b)
-    r = b.copy()
+def pcg_steps(K, b, M, k, x0=None):
+    """k steps of the preconditioned CG recurrence from x0 (default 0) (MGPIS::CG_SOLV, no stop rule)"""
+    x = np.zeros_like(b) if x0 is None else np.array(x0, dtype=np.float64)
+    r = b.copy() if x0 is None else b - K @ x
     z = M(r)
     p = z.copy()
     rz = r @ z
@@ -613,6 +613,9 @@ def parity_cases():
 
 
 _MESH = {}
+# the dehw generator's uneven chain (group g is 1 + g mod 3 blocks long): twelve subdomains of three
+# sizes, three levels, every size ending in a partial 64-node chunk ("u", test_batch_parity_gpu.py)
+UNEVEN_CHAIN = ("dehw", 6, 2, 2, 1, 2, 0.3, 0, 0, 0, 0, 1)
 
 
 def load_mesh(ddpca, mesh, tv):
@@ -620,16 +623,18 @@ def load_mesh(ddpca, mesh, tv):
     key = (mesh, tv)
     if key in _MESH:
         return _MESH[key]
-    if mesh in ("h2", "h3", "g3"):
+    if mesh in ("h2", "h3", "g3", "u"):
         pk = ("problem", mesh)
         if pk not in _MESH:
-            _MESH[pk] = ddpca.headline_problem(gl=2 if mesh == "h2" else 3,
-                                               **(ddpca.GENERAL_FEATURES if mesh == "g3" else {})).ESTABLISH()
+            _MESH[pk] = ddpca.Problem(*UNEVEN_CHAIN).ESTABLISH() if mesh == "u" else \
+                ddpca.headline_problem(gl=2 if mesh == "h2" else 3,
+                                       **(ddpca.GENERAL_FEATURES if mesh == "g3" else {})).ESTABLISH()
         P = _MESH[pk]
         K, Pr, fdof, nn = hierarchy(P, tv)
         co = np.asarray(P.array("coords", tv), dtype=np.float64).reshape(-1, 3)
         b = np.asarray(P.grid(tv).consForc, dtype=np.float64)
-        m = dict(K=K, P=Pr, fdof=fdof, nn=nn, coords=co, b=b, create=lambda **o: ddpca.MGPIS.from_problem(P, tv, **o))
+        m = dict(K=K, P=Pr, fdof=fdof, nn=nn, coords=co, b=b, problem=P,
+                 create=lambda **o: ddpca.MGPIS.from_problem(P, tv, **o))
     elif mesh == "csr_s2":
         from conftest import CASE_PARAMS
         P = ddpca.Problem(*CASE_PARAMS["beam_s2"]).ESTABLISH()
