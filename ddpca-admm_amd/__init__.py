@@ -129,6 +129,11 @@ def _declare(L: C.CDLL) -> None:
                                        C.c_double, C.POINTER(_P)]
     L.ddpca_refine_select.argtypes = [_P, C.c_int64, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P,
                                       C.c_double, C.c_int64, _P, C.c_int64, _P, _P, _P]
+    L.ddpca_contact_search_on.argtypes = [C.c_int, *L.ddpca_contact_search.argtypes]
+    L.ddpca_refine_select_on.argtypes = [C.c_int, *L.ddpca_refine_select.argtypes]
+    L.ddpca_csearch_last_ms.argtypes = [_DP]
+    L.ddpca_csearch_last_pairs.argtypes = [_I64P]
+    L.ddpca_csearch_last_pairs.restype = C.c_int64
     L.ddpca_ips_count.argtypes = [_P]
     L.ddpca_ips_count.restype = C.c_int64
     L.ddpca_ips_get.argtypes = [_P, _P, _P, _P, _P, _P]
@@ -514,30 +519,80 @@ class Problem:
         return subs, ifaces
 
 
-def contact_search(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck, maxiDist: float = 1.0e12) -> dict:
-    """CSEARCH::BUCKET_SORT + CONTACT_SEARCH (CSEARCH.h:205-230, 777-817): integration points of
-    the contact between master faces (mast_segm, 4 node ids each, coordinates mast_xyz by node id,
-    2-D bucket coordinates mast_2d) and slave faces, in the reference's order.  Returns node
-    (n, 2, 4), shap (n, 2, 4), basis (n, 3, 3), gap (n), w (n) -- Problem.set_ips' arguments."""
+def _csearch_args(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck):
+    """The face / bucket arguments of ddpca_contact_search and ddpca_refine_select (and the arrays
+    that own their memory)."""
     def a(x, dt):
         return np.ascontiguousarray(x, dtype=dt)
     mx, sx = a(mast_xyz, np.float64).reshape(-1), a(slav_xyz, np.float64).reshape(-1)
     ms, ss = a(mast_segm, np.int64).reshape(-1), a(slav_segm, np.int64).reshape(-1)
     m2, s2 = a(mast_2d, np.float64).reshape(-1), a(slav_2d, np.float64).reshape(-1)
     bk = a(buck, np.int64)
+    keep = (mx, sx, ms, ss, m2, s2, bk)
+    return (_ptr(mx), len(mx) // 3, _ptr(sx), len(sx) // 3, len(ms) // 4, _ptr(ms), _ptr(m2), len(ss) // 4, _ptr(ss),
+            _ptr(s2), _ptr(bk)), keep
+
+
+def contact_search(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck, maxiDist: float = 1.0e12,
+                   device=None) -> dict:
+    """CSEARCH::BUCKET_SORT + CONTACT_SEARCH (CSEARCH.h:205-230, 777-817): integration points of
+    the contact between master faces (mast_segm, 4 node ids each, coordinates mast_xyz by node id,
+    2-D bucket coordinates mast_2d) and slave faces, in the reference's order.  Returns node
+    (n, 2, 4), shap (n, 2, 4), basis (n, 3, 3), gap (n), w (n) -- Problem.set_ips' arguments.
+    device: None, the host search (ddpca_contact_search); an int, ddpca_contact_search_on -- a GPU
+    index, -1 (the same host search) or -2 (the device path's steps on the host)."""
+    args, keep = _csearch_args(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck)
     h = C.c_void_p()
-    _check(lib().ddpca_contact_search(_ptr(mx), len(mx) // 3, _ptr(sx), len(sx) // 3, len(ms) // 4, _ptr(ms), _ptr(m2),
-                                      len(ss) // 4, _ptr(ss), _ptr(s2), _ptr(bk), float(maxiDist), C.byref(h)))
+    if device is None:
+        _check(lib().ddpca_contact_search(*args, float(maxiDist), C.byref(h)))
+    else:
+        _check(lib().ddpca_contact_search_on(int(device), *args, float(maxiDist), C.byref(h)))
     try:
         n = int(lib().ddpca_ips_count(h))
-        out = dict(node=np.zeros((n, 2, 4), np.int64), shap=np.zeros((n, 2, 4)), basis=np.zeros((n, 3, 3)),
-                   gap=np.zeros(n), w=np.zeros(n))
+        out = dict(node=np.empty((n, 2, 4), np.int64), shap=np.empty((n, 2, 4)), basis=np.empty((n, 3, 3)),
+                   gap=np.empty(n), w=np.empty(n))  # ddpca_ips_get writes every element
         if n:
             _check(lib().ddpca_ips_get(h, _ptr(out["node"]), _ptr(out["shap"]), _ptr(out["basis"]), _ptr(out["gap"]),
                                        _ptr(out["w"])))
         return out
     finally:
         lib().ddpca_ips_destroy(h)
+
+
+def refine_select(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck, distCrit: float, mast_elem, slav_elem,
+                  device=None):
+    """CSEARCH::ADAPTIVE_REFINE's selection (CSEARCH.h:839-956): with contact_search's face / bucket
+    arguments, every node of the integration points of face pairs that come within distCrit is a
+    split node, and a candidate element (mast_elem / slav_elem: 8 corner node ids each) with a split
+    corner is flagged.  Returns (any, mast_split, slav_split): the reference's isnoRefi and one bool
+    per element.  device as in contact_search (None: ddpca_refine_select; an int:
+    ddpca_refine_select_on)."""
+    args, keep = _csearch_args(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck)
+    me = np.ascontiguousarray(mast_elem, dtype=np.int64).reshape(-1)
+    se = np.ascontiguousarray(slav_elem, dtype=np.int64).reshape(-1)
+    mf, sf = np.zeros(len(me) // 8, np.uint8), np.zeros(len(se) // 8, np.uint8)
+    tail = (float(distCrit), len(mf), _ptr(me), len(sf), _ptr(se), _ptr(mf), _ptr(sf))
+    if device is None:
+        rc = _check(lib().ddpca_refine_select(*args, *tail))
+    else:
+        rc = _check(lib().ddpca_refine_select_on(int(device), *args, *tail))
+    return bool(rc), mf.astype(bool), sf.astype(bool)
+
+
+def csearch_last_ms() -> tuple:
+    """Of this thread's last two-pass contact search (device >= 0 or -2), in ms: plan, upload,
+    k_cs_count + scan, k_cs_emit, copy back (ddpca_csearch_last_ms; measurement only)."""
+    out = (C.c_double * 5)()
+    _check(lib().ddpca_csearch_last_ms(out))
+    return tuple(out)
+
+
+def csearch_last_pairs() -> tuple:
+    """Candidate pairs, kept pairs and points of this thread's last two-pass contact search
+    (ddpca_csearch_last_pairs)."""
+    out = (C.c_int64 * 3)()
+    _check(int(lib().ddpca_csearch_last_pairs(out)))
+    return tuple(int(x) for x in out)
 
 
 class LAGRANGE:
@@ -1274,7 +1329,7 @@ class MCONTACT:
 
 
 __all__ = ["Problem", "MULTIGRID", "TreeMultigrid", "write_resuStre", "write_resuFreq", "MGPIS", "MCONTACT", "DdpcaError", "lib", "gpu_available", "default_options",
-           "contact_search", "mass_solve", "stream_ceiling", "probe_grid_barrier",
+           "contact_search", "refine_select", "csearch_last_ms", "csearch_last_pairs", "mass_solve", "stream_ceiling", "probe_grid_barrier",
            "LIBPATH", "HEADLINE_OPTIONS", "HEADLINE_OPTIONS_SMALL", "headline_options", "HEADLINE_MUSC",
            "HEADLINE_WORKLOAD",
            "headline_problem"]

@@ -20,8 +20,12 @@
 #include <string>
 #include <vector>
 
+#include <chrono>
+
 #include "../../include/ddpca_amd.h"
 #include "common.hpp"
+#include "csearch_face.hpp"
+#include "device_csearch.hpp"
 #include "mcontact.hpp"
 
 using namespace ddpca;
@@ -371,9 +375,222 @@ std::vector<std::vector<IntegralPoint>> search(const double* mast_xyz, int64_t m
 
 }  // namespace
 
-struct ddpca_ips {
-    std::vector<IntegralPoint> ip;
-};
+namespace {
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void face_corners(const double* xyz, const int32_t* seg, double (&c)[4][3]) {
+    for (int k = 0; k < 4; ++k)
+        for (int a = 0; a < 3; ++a) c[k][a] = xyz[3 * (int64_t)seg[k] + a];
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// The two-pass search: the plan (here, on the host), then count / scan / emit over the candidate
+// pairs with the arithmetic of csearch_face.hpp -- on the device (device_csearch.hip) or, for
+// device = -2, below.  search() above stays the default and the specification.
+// ---------------------------------------------------------------------------------------------
+namespace ddpca {
+
+CsearchPlan csearch_plan(const CsearchInput& in) {
+    const int64_t nm = in.nm, ns = in.ns;
+    const int64_t* buck = in.buck;
+    if (!in.mast_xyz || !in.slav_xyz || !in.mast_segm || !in.slav_segm || !in.mast_2d || !in.slav_2d || !buck || nm < 1 || ns < 0)
+        throw ApiError(DDPCA_EINVAL, "null argument / no master faces");
+    if (buck[0] < 1 || buck[1] < 1) throw ApiError(DDPCA_EINVAL, "bucket counts >= 1");
+    const int64_t lim = (int64_t)1 << 31;
+    if (in.mast_nnode >= lim || in.slav_nnode >= lim || nm >= lim || ns >= lim || buck[0] >= lim || buck[1] >= lim ||
+        buck[0] * buck[1] >= lim)
+        throw ApiError(DDPCA_EINVAL, "contact search: the two-pass path takes fewer than 2^31 nodes, faces and buckets");
+    for (int64_t i = 0; i < 4 * nm; ++i)
+        if (in.mast_segm[i] < 0 || in.mast_segm[i] >= in.mast_nnode) throw ApiError(DDPCA_EINVAL, "master face node out of range");
+    for (int64_t i = 0; i < 4 * ns; ++i)
+        if (in.slav_segm[i] < 0 || in.slav_segm[i] >= in.slav_nnode) throw ApiError(DDPCA_EINVAL, "slave face node out of range");
+    // what a bounded kernel needs beyond search()'s checks
+    auto finite = [](const double* v, int64_t n) {
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(v[i])) return false;
+        return true;
+    };
+    if (!finite(in.mast_xyz, 3 * in.mast_nnode) || !finite(in.slav_xyz, 3 * in.slav_nnode) || !finite(in.mast_2d, 2 * nm) ||
+        !finite(in.slav_2d, 2 * ns))
+        throw ApiError(DDPCA_EINVAL, "contact search: non-finite coordinate");
+    CsearchPlan P;
+    P.mast_face.resize((size_t)4 * nm);
+    P.slav_face.resize((size_t)4 * ns);
+    for (int64_t i = 0; i < 4 * nm; ++i) P.mast_face[i] = (int32_t)in.mast_segm[i];
+    for (int64_t i = 0; i < 4 * ns; ++i) P.slav_face[i] = (int32_t)in.slav_segm[i];
+    // the trip cap of PROJECT_STM's stepped approach: no point is farther from a face's corner mean
+    // than the bounding-box diagonal of all nodes, and a step is the face's shortest corner distance
+    double diam = 1.0e300;
+    for (int64_t m = 0; m < nm; ++m) {
+        double c[4][3], cent[3];
+        face_corners(in.mast_xyz, &P.mast_face[4 * m], c);
+        const double d = csface::face_diam(c, cent);
+        if (!(d > 0.0)) throw ApiError(DDPCA_EINVAL, "contact search: master face " + std::to_string(m) + " has two coincident corners");
+        diam = std::min(diam, d);
+    }
+    double lo3[3], hi3[3];
+    for (int a = 0; a < 3; ++a) lo3[a] = hi3[a] = in.mast_xyz[a];
+    for (int side = 0; side < 2; ++side) {
+        const double* xyz = side ? in.slav_xyz : in.mast_xyz;
+        const int64_t nn = side ? in.slav_nnode : in.mast_nnode;
+        for (int64_t i = 0; i < nn; ++i)
+            for (int a = 0; a < 3; ++a) lo3[a] = std::min(lo3[a], xyz[3 * i + a]), hi3[a] = std::max(hi3[a], xyz[3 * i + a]);
+    }
+    const double diag = std::sqrt((hi3[0] - lo3[0]) * (hi3[0] - lo3[0]) + (hi3[1] - lo3[1]) * (hi3[1] - lo3[1]) +
+                                  (hi3[2] - lo3[2]) * (hi3[2] - lo3[2]));
+    const double cap = diag / diam + 1.0;
+    if (!(cap <= (double)kCsearchMaxCap))
+        throw ApiError(DDPCA_EINVAL, "contact search: the interface is " + std::to_string(diag / diam) +
+                                         " times its smallest master face edge (limit 2^20)");
+    P.cap = (long)cap + 1;
+    // BUCKET_SORT with search()'s expressions
+    double lo[2], step[2];
+    for (int a = 0; a < 2; ++a) {
+        double mn = in.mast_2d[a], mx = in.mast_2d[a];
+        for (int64_t i = 0; i < nm; ++i) mn = std::min(mn, in.mast_2d[2 * i + a]), mx = std::max(mx, in.mast_2d[2 * i + a]);
+        double inc = (mx - mn) / (double)buck[a];
+        if (std::abs(inc) < 1.0e-10) inc = 1.0e-10;
+        lo[a] = mn - inc;
+        step[a] = ((mx + inc) - lo[a]) / (double)buck[a];
+    }
+    const int64_t nb = buck[0] * buck[1];
+    std::vector<int64_t> mcell((size_t)nm);
+    P.bucket_ptr.assign((size_t)nb + 1, 0);
+    for (int64_t i = 0; i < nm; ++i) {
+        const long r = (long)((in.mast_2d[2 * i] - lo[0]) / step[0]), c = (long)((in.mast_2d[2 * i + 1] - lo[1]) / step[1]);
+        if (r < 0 || r > buck[0] - 1 || c < 0 || c > buck[1] - 1)  // by construction of lo / step it is inside
+            throw ApiError(DDPCA_EINVAL, "contact search: master face outside the bucket grid");
+        mcell[i] = r * buck[1] + c;
+        ++P.bucket_ptr[mcell[i] + 1];
+    }
+    for (int64_t b = 0; b < nb; ++b) P.bucket_ptr[b + 1] += P.bucket_ptr[b];
+    P.bucket_face.resize((size_t)nm);
+    {
+        std::vector<int64_t> fill(P.bucket_ptr.begin(), P.bucket_ptr.end() - 1);
+        for (int64_t i = 0; i < nm; ++i) P.bucket_face[fill[mcell[i]]++] = (int32_t)i;
+    }
+    // CONTACT_SEARCH's candidates: slave faces in order, each over its 3 x 3 buckets
+    P.cell.assign((size_t)ns, -1);
+    P.pair_off.assign((size_t)ns + 1, 0);
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int64_t t = 0; t < ns; ++t) {
+            const long r = (long)((in.slav_2d[2 * t] - lo[0]) / step[0]), c = (long)((in.slav_2d[2 * t + 1] - lo[1]) / step[1]);
+            if (r < 0 || r > buck[0] - 1 || c < 0 || c > buck[1] - 1) continue;
+            P.cell[t] = r * buck[1] + c;
+            int64_t q = pass == 0 ? 0 : P.pair_off[t];
+            for (long j = std::max(r - 1, 0L); j <= std::min(r + 1, (long)buck[0] - 1); ++j)
+                for (long k = std::max(c - 1, 0L); k <= std::min(c + 1, (long)buck[1] - 1); ++k) {
+                    const int64_t b = j * buck[1] + k;
+                    if (pass == 0) {
+                        q += P.bucket_ptr[b + 1] - P.bucket_ptr[b];
+                    } else {
+                        for (int64_t e = P.bucket_ptr[b]; e < P.bucket_ptr[b + 1]; ++e, ++q) {
+                            P.pair_slav[q] = (int32_t)t;
+                            P.pair_mast[q] = P.bucket_face[e];
+                        }
+                    }
+                }
+            if (pass == 0) P.pair_off[t + 1] = q;
+        }
+        if (pass == 0) {
+            for (int64_t t = 0; t < ns; ++t) P.pair_off[t + 1] += P.pair_off[t];
+            P.pair_slav.resize((size_t)P.pair_off[ns]);
+            P.pair_mast.resize((size_t)P.pair_off[ns]);
+        }
+    }
+    return P;
+}
+
+void csearch_two_pass_host(const CsearchInput& in, bool values, ddpca_ips& out, double ms[5], int64_t pairs[3]) {
+    auto t0 = std::chrono::steady_clock::now();
+    const CsearchPlan P = csearch_plan(in);
+    ms[0] = ms_since(t0), ms[1] = 0.0, ms[4] = 0.0;
+    t0 = std::chrono::steady_clock::now();
+    const int64_t np = (int64_t)P.pair_slav.size();
+    std::vector<int32_t> count((size_t)np);
+#pragma omp parallel for schedule(dynamic, 256)
+    for (int64_t p = 0; p < np; ++p) {
+        double mc[4][3], sc[4][3], sx[csface::kMaxClip], sy[csface::kMaxClip], sa[csface::kMaxClip], cx, cy;
+        face_corners(in.mast_xyz, &P.mast_face[4 * (int64_t)P.pair_mast[p]], mc);
+        face_corners(in.slav_xyz, &P.slav_face[4 * (int64_t)P.pair_slav[p]], sc);
+        count[p] = csface::pair_count(mc, sc, P.cap, in.maxiDist, csface::Slots{sx, sy, sa, 1}, cx, cy);
+    }
+    // exclusive scan over the kept pairs
+    std::vector<int64_t> kept, off;
+    int64_t total = 0;
+    for (int64_t p = 0; p < np; ++p)
+        if (count[p] > 0) {
+            kept.push_back(p);
+            off.push_back(total);
+            total += count[p];
+        }
+    ms[2] = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    out.resize(total, values);
+    const int64_t nk = (int64_t)kept.size();
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t e = 0; e < nk; ++e) {
+        const int64_t p = kept[e];
+        const int32_t* mn = &P.mast_face[4 * (int64_t)P.pair_mast[p]];
+        const int32_t* sn = &P.slav_face[4 * (int64_t)P.pair_slav[p]];
+        double mc[4][3], sc[4][3], g[4][3], sx[csface::kMaxClip], sy[csface::kMaxClip], sa[csface::kMaxClip], cx, cy;
+        face_corners(in.mast_xyz, mn, mc);
+        face_corners(in.slav_xyz, sn, sc);
+        const csface::Slots S{sx, sy, sa, 1};
+        const int n = csface::polygon(mc, sc, P.cap, S, cx, cy);
+        csface::bilinear(sc, g);
+        for (int q = 0; q < 4 * n; ++q) {
+            const int64_t o = off[e] + q;
+            for (int k = 0; k < 4; ++k) out.node[8 * o + k] = mn[k], out.node[8 * o + 4 + k] = sn[k];
+            if (!values) continue;
+            double px, py, wq;
+            csface::quad_point(S, n, cx, cy, q, px, py, wq);
+            csface::Point pt;
+            csface::point(mc, sc, g, px, py, wq, pt);
+            for (int s = 0; s < 2; ++s)
+                for (int k = 0; k < 4; ++k) out.shap[8 * o + 4 * s + k] = pt.shap[s][k];
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) out.basis[9 * o + 3 * a + b] = pt.basis[a][b];
+            out.gap[o] = pt.gap;
+            out.w[o] = pt.w;
+        }
+    }
+    ms[3] = ms_since(t0);
+    pairs[0] = np, pairs[1] = nk, pairs[2] = total;
+}
+
+int refine_flags(const ddpca_ips& ips, int64_t mast_nnode, int64_t slav_nnode, int64_t ne_m, const int64_t* mast_elem,
+                 int64_t ne_s, const int64_t* slav_elem, uint8_t* mast_split, uint8_t* slav_split) {
+    if ((ne_m > 0 && (!mast_elem || !mast_split)) || (ne_s > 0 && (!slav_elem || !slav_split)) || ne_m < 0 || ne_s < 0)
+        throw ApiError(DDPCA_EINVAL, "null argument");
+    // every node of the kept pairs' points is a split node (as ddpca_refine_select)
+    std::vector<uint8_t> split[2] = {std::vector<uint8_t>(mast_nnode, 0), std::vector<uint8_t>(slav_nnode, 0)};
+    for (int64_t q = 0; q < ips.n; ++q)
+        for (int s = 0; s < 2; ++s)
+            for (int k = 0; k < 4; ++k) split[s][ips.node[8 * q + 4 * s + k]] = 1;
+    const int64_t ne[2] = {ne_m, ne_s};
+    const int64_t* el[2] = {mast_elem, slav_elem};
+    uint8_t* fl[2] = {mast_split, slav_split};
+    const int64_t nn[2] = {mast_nnode, slav_nnode};
+    for (int s = 0; s < 2; ++s)
+        for (int64_t e = 0; e < ne[s]; ++e) {
+            uint8_t f = 0;
+            for (int k = 0; k < 8; ++k) {
+                const int64_t n = el[s][8 * e + k];
+                if (n < 0 || n >= nn[s]) throw ApiError(DDPCA_EINVAL, "element corner node out of range");
+                f |= split[s][n];
+            }
+            fl[s][e] = f;
+        }
+    return ips.n > 0 ? 1 : 0;
+}
+
+}  // namespace ddpca
 
 extern "C" {
 
@@ -388,8 +605,21 @@ int ddpca_contact_search(const double* mast_xyz, int64_t mast_nnode, const doubl
         auto R = std::make_unique<ddpca_ips>();
         size_t total = 0;
         for (const auto& v : per) total += v.size();
-        R->ip.reserve(total);
-        for (auto& v : per) R->ip.insert(R->ip.end(), v.begin(), v.end());
+        R->resize((int64_t)total, true);
+        int64_t q = 0;
+        for (const auto& v : per)
+            for (const IntegralPoint& p : v) {
+                for (int s = 0; s < 2; ++s)
+                    for (int k = 0; k < 4; ++k) {
+                        R->node[8 * q + 4 * s + k] = p.node[s][k];
+                        R->shap[8 * q + 4 * s + k] = p.shap[s][k];
+                    }
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < 3; ++b) R->basis[9 * q + 3 * a + b] = p.basis[a][b];
+                R->gap[q] = p.gap;
+                R->w[q] = p.w;
+                ++q;
+            }
         *out = R.release();
     });
 }
@@ -433,25 +663,20 @@ int ddpca_refine_select(const double* mast_xyz, int64_t mast_nnode, const double
     return rc != 0 ? rc : any;
 }
 
-int64_t ddpca_ips_count(ddpca_ips_t h) { return h ? (int64_t)h->ip.size() : -1; }
+int64_t ddpca_ips_count(ddpca_ips_t h) { return h ? h->n : -1; }
 
 int ddpca_ips_get(ddpca_ips_t h, int64_t* node, double* shap, double* basis, double* gap, double* w) {
     return guarded([&] {
         if (!h) throw ApiError(DDPCA_EINVAL, "null handle");
-        const int64_t n = (int64_t)h->ip.size();
-        for (int64_t q = 0; q < n; ++q) {
-            const IntegralPoint& p = h->ip[q];
-            for (int s = 0; s < 2; ++s)
-                for (int k = 0; k < 4; ++k) {
-                    if (node) node[8 * q + 4 * s + k] = p.node[s][k];
-                    if (shap) shap[8 * q + 4 * s + k] = p.shap[s][k];
-                }
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b)
-                    if (basis) basis[9 * q + 3 * a + b] = p.basis[a][b];
-            if (gap) gap[q] = p.gap;
-            if (w) w[q] = p.w;
-        }
+        const size_t n = (size_t)h->n;
+        if (n == 0) return;
+        if ((shap || basis || gap || w) && !h->values)
+            throw ApiError(DDPCA_ESTATE, "ddpca_ips_get: this search kept the node ids only");
+        if (node) std::memcpy(node, h->node.get(), 8 * n * sizeof(int64_t));
+        if (shap) std::memcpy(shap, h->shap.get(), 8 * n * sizeof(double));
+        if (basis) std::memcpy(basis, h->basis.get(), 9 * n * sizeof(double));
+        if (gap) std::memcpy(gap, h->gap.get(), n * sizeof(double));
+        if (w) std::memcpy(w, h->w.get(), n * sizeof(double));
     });
 }
 

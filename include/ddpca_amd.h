@@ -269,6 +269,39 @@ int64_t ddpca_ips_count(ddpca_ips_t h);
 /* node[n][2][4], shap[n][2][4], basis[n][3][3] (n, t1, t2), gap[n], w[n]; any pointer may be NULL */
 int ddpca_ips_get(ddpca_ips_t h, int64_t* node, double* shap, double* basis, double* gap, double* w);
 int ddpca_ips_destroy(ddpca_ips_t h);
+/* The same search / selection on a chosen path (CSEARCH.h:205-230, 614-817, 839-956): `device`, then
+ * the arguments of ddpca_contact_search / ddpca_refine_select.
+ *   device >= 0  the face pairs on that GPU.  The host builds the plan (bucket sort, the candidate
+ *                pairs in the reference's order), k_cs_count evaluates every pair to its point
+ *                count, the counts are scanned, k_cs_emit writes the kept pairs' points at their
+ *                offsets: the same points in the same order as the host search, values equal up to
+ *                rounding-level choices (which of two points closer than 1e-10 the clip keeps, the
+ *                last bit of atan2).  Every device buffer lives for the call; a failed allocation is
+ *                DDPCA_EHIP with what was being allocated and its size.  No host fallback.
+ *   device = -1  the host entries above, unchanged.
+ *   device = -2  the device path's own steps on the host: its plan, count / scan / emit and the
+ *                shared face arithmetic (csearch_face.hpp), OpenMP over pairs.  It exists so that
+ *                everything but the launch can be tested and sanitized without a GPU.
+ * On the two-pass paths (>= 0 and -2) a kernel must not spin where the host search would: a
+ * non-finite coordinate, a master face with two coincident corners, and an interface more than
+ * 2^20 times its smallest master face edge (the trip cap of PROJECT_STM's stepped approach,
+ * CSEARCH.h:401-428) are DDPCA_EINVAL before anything is launched, as are 2^31 or more nodes, faces
+ * or candidate pairs.  ddpca_refine_select_on brings back the node ids of the kept pairs only. */
+int ddpca_contact_search_on(int device, const double* mast_xyz, int64_t mast_nnode, const double* slav_xyz,
+                            int64_t slav_nnode, int64_t nm, const int64_t* mast_segm, const double* mast_2d, int64_t ns,
+                            const int64_t* slav_segm, const double* slav_2d, const int64_t* buck, double maxiDist,
+                            ddpca_ips_t* out);
+int ddpca_refine_select_on(int device, const double* mast_xyz, int64_t mast_nnode, const double* slav_xyz,
+                           int64_t slav_nnode, int64_t nm, const int64_t* mast_segm, const double* mast_2d, int64_t ns,
+                           const int64_t* slav_segm, const double* slav_2d, const int64_t* buck, double distCrit,
+                           int64_t ne_m, const int64_t* mast_elem, int64_t ne_s, const int64_t* slav_elem,
+                           uint8_t* mast_split, uint8_t* slav_split);
+/* Of the calling thread's last two-pass search (measurement only).  out5 (ms): plan (host clock),
+ * upload (host clock), k_cs_count by HIP events + the copy of the counts and their scan on the host,
+ * k_cs_emit by HIP events, copy back (host clock); on -2 the host clock of plan, count + scan and
+ * emit, the others 0.  out3: candidate pairs, kept pairs, points. */
+int ddpca_csearch_last_ms(double* out5);
+int64_t ddpca_csearch_last_pairs(int64_t* out3);
 /* Coarse-space setting of MCONTACT (muscSett / doleMcsc, MCONTACT.h:22-23), before establish.
  * muscSett = 2 selects the interface-eliminated coarse space (MULTISCALE_1, MCONTACT.h:
  * 1672-2301; the examples' choice, e.g. BLOCK.h:38, TORSION.h:39, DEHW.h:2222), built by
