@@ -38,7 +38,8 @@ struct SellArgs {
     const int64_t* off;
     const int32_t* col;
     const int16_t* col16;  // column offsets from the row node (levels whose offsets fit), or null
-    const void* val;       // double (Krylov operator) or float (fp32-stored V-cycle operator)
+    const void* val;       // streamed values in the launch's ValType: double (Krylov operator), or the V-cycle
+                           // copy's float / block-exponent fp16 / block-scaled int8; null in table mode
     const int32_t* csub;   // chunk -> subdomain
     int64_t nch;
     const double* x;       // gathered operand
@@ -914,10 +915,27 @@ __global__ __launch_bounds__(kBlock) void k_restrict_lat(const RT* rf, const uin
     restrict_store<INIT, BJ, SETD>(cmask, bc, xc, dc, minv, coef, j, sub, s0, s1, s2, xc4);
 }
 
-// x_f += mask_f (P e_c)
-template <bool UW = false>  // UW: weights 1 / parent count (see k_restrict), pw unread
+// x_f += mask_f e into a level's fp64 iterate ...
+__device__ __forceinline__ void masked_add(double* xf, int64_t i, uint8_t m, double e0, double e1, double e2) {
+    if (m & 1) xf[3 * i] += e0;
+    if (m & 2) xf[3 * i + 1] += e1;
+    if (m & 4) xf[3 * i + 2] += e2;
+}
+// ... or into its fp32 iterate copy (LevelDev::x4a of a block-Jacobi level, GsFine::x4 of the
+// multicolour sweeps): the add in fp64, the copy rounded once on store
+__device__ __forceinline__ void masked_add(float4* x4, int64_t i, uint8_t m, double e0, double e1, double e2) {
+    float4 v = x4[i];
+    if (m & 1) v.x = (float)((double)v.x + e0);
+    if (m & 2) v.y = (float)((double)v.y + e1);
+    if (m & 4) v.z = (float)((double)v.z + e2);
+    x4[i] = v;
+}
+
+// x_f += mask_f (P e_c); XT: the fine iterate (double) or its fp32 copy (float4, see masked_add),
+// the sum in fp64 either way
+template <bool UW = false, typename XT = double>  // UW: weights 1 / parent count (see k_restrict), pw unread
 __global__ __launch_bounds__(kBlock) void k_prolong(const double* ec, const int32_t* ppar, const double* pw,
-                                                    const uint8_t* fmask, double* xf, int64_t nf, const int32_t* csub,
+                                                    const uint8_t* fmask, XT* xf, int64_t nf, const int32_t* csub,
                                                     const PcgScal* sc) {
     NODE_PROLOGUE(nf, csub, sc)
     double e0 = 0.0, e1 = 0.0, e2 = 0.0;
@@ -938,49 +956,16 @@ __global__ __launch_bounds__(kBlock) void k_prolong(const double* ec, const int3
         e1 *= w;
         e2 *= w;
     }
-    const uint8_t m = fmask[i];
-    if (m & 1) xf[3 * i] += e0;
-    if (m & 2) xf[3 * i + 1] += e1;
-    if (m & 4) xf[3 * i + 2] += e2;
-}
-
-// the same into a block-Jacobi level's fp32 iterate copy (LevelDev::x4a): the sum and the add in fp64
-template <bool UW = false>
-__global__ __launch_bounds__(kBlock) void k_prolong_x4(const double* ec, const int32_t* ppar, const double* pw,
-                                                       const uint8_t* fmask, float4* x4, int64_t nf, const int32_t* csub,
-                                                       const PcgScal* sc) {
-    NODE_PROLOGUE(nf, csub, sc)
-    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
-    int np = 0;
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const int32_t c = ppar[p * nf + i];
-        if (c < 0) break;
-        const double w = UW ? 1.0 : pw[p * nf + i];
-        e0 += w * ec[3 * (int64_t)c];
-        e1 += w * ec[3 * (int64_t)c + 1];
-        e2 += w * ec[3 * (int64_t)c + 2];
-        ++np;
-    }
-    if (UW) {
-        const double w = kInvCount[np];
-        e0 *= w;
-        e1 *= w;
-        e2 *= w;
-    }
-    const uint8_t m = fmask[i];
-    float4 v = x4[i];
-    if (m & 1) v.x = (float)((double)v.x + e0);
-    if (m & 2) v.y = (float)((double)v.y + e1);
-    if (m & 4) v.z = (float)((double)v.z + e2);
-    x4[i] = v;
+    masked_add(xf, i, fmask[i], e0, e1, e2);
 }
 
 // Lattice prolongation (LevelDev::lat): parents p0 + the subset sums of the coarse strides the
 // node's code selects, weight 1 / 2^popcount(code); one 4-B word per fine node, the (up to 8)
-// parent gathers independent of each other
+// parent gathers independent of each other.  XT = float4: x4_f = fp32(x4_f + mask_f 2^-k sum e_c)
+// into the multicolour sweeps' copy (what the backward sweep then gathers) or a block-Jacobi level's
+template <typename XT = double>
 __global__ __launch_bounds__(kBlock) void k_prolong_lat(const double* ec, const uint32_t* ppk, const int32_t* pstr,
-                                                        const uint8_t* fmask, double* xf, int64_t nf,
+                                                        const uint8_t* fmask, XT* xf, int64_t nf,
                                                         const int32_t* csub, const PcgScal* sc) {
     NODE_PROLOGUE(nf, csub, sc)
     const uint32_t w = ppk[i];
@@ -1001,46 +986,15 @@ __global__ __launch_bounds__(kBlock) void k_prolong_lat(const double* ec, const 
         e2 += w * ec[3 * c + 2];
     }
     const double wt = 1.0 / (double)(1 << __popc(code));
-    const uint8_t m = fmask[i];
-    if (m & 1) xf[3 * i] += wt * e0;
-    if (m & 2) xf[3 * i + 1] += wt * e1;
-    if (m & 4) xf[3 * i + 2] += wt * e2;
-}
-
-// The same into the multicolour sweeps' fp32 iterate copy (GsFine::x4): x4_f = fp32(x4_f + mask_f
-// 2^-k sum e_c), the sum and the add in fp64 -- what the backward sweep then gathers
-__global__ __launch_bounds__(kBlock) void k_prolong_lat_x4(const double* ec, const uint32_t* ppk, const int32_t* pstr,
-                                                           const uint8_t* fmask, float4* x4, int64_t nf,
-                                                           const int32_t* csub, const PcgScal* sc) {
-    NODE_PROLOGUE(nf, csub, sc)
-    const uint32_t w = ppk[i];
-    const int64_t p0 = w & 0x1fffffffu;
-    const uint32_t code = w >> 29;
-    const int64_t s0 = pstr[3 * sub], s1 = pstr[3 * sub + 1], s2 = pstr[3 * sub + 2];
-    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
-#pragma unroll
-    for (uint32_t q = 0; q < 8; ++q) {
-        const bool in = (q & ~code) == 0;
-        const int64_t c = in ? p0 + ((q & 1) ? s0 : 0) + ((q & 2) ? s1 : 0) + ((q & 4) ? s2 : 0) : p0;
-        const double w = in ? 1.0 : 0.0;
-        e0 += w * ec[3 * c];
-        e1 += w * ec[3 * c + 1];
-        e2 += w * ec[3 * c + 2];
-    }
-    const double wt = 1.0 / (double)(1 << __popc(code));
-    const uint8_t m = fmask[i];
-    float4 v = x4[i];
-    if (m & 1) v.x = (float)((double)v.x + wt * e0);
-    if (m & 2) v.y = (float)((double)v.y + wt * e1);
-    if (m & 4) v.z = (float)((double)v.z + wt * e2);
-    x4[i] = v;
+    masked_add(xf, i, fmask[i], wt * e0, wt * e1, wt * e2);
 }
 
 // Block transfer entries (rotated nodes): x_f += mask_f (B e_c) per fine node that owns one
-// (after k_prolong, whose weight for those entries is 0); thread = fine node.
+// (after k_prolong, whose weight for those entries is 0); thread = fine node.  XT as in k_prolong
+template <typename XT = double>
 __global__ __launch_bounds__(kBlock) void k_prolong_rot(const double* ec, const int32_t* row, const int64_t* ptr,
                                                         const int32_t* par, const double* blk, const uint8_t* fmask,
-                                                        double* xf, int64_t nr, const int32_t* csub,
+                                                        XT* xf, int64_t nr, const int32_t* csub,
                                                         const PcgScal* sc) {
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (t >= nr) return;
@@ -1055,36 +1009,7 @@ __global__ __launch_bounds__(kBlock) void k_prolong_rot(const double* ec, const 
         e1 += B[3] * c0 + B[4] * c1 + B[5] * c2;
         e2 += B[6] * c0 + B[7] * c1 + B[8] * c2;
     }
-    const uint8_t m = fmask[i];
-    if (m & 1) xf[3 * i] += e0;
-    if (m & 2) xf[3 * i + 1] += e1;
-    if (m & 4) xf[3 * i + 2] += e2;
-}
-
-// the same into a block-Jacobi level's fp32 iterate copy (LevelDev::x4a), after k_prolong_x4
-__global__ __launch_bounds__(kBlock) void k_prolong_rot_x4(const double* ec, const int32_t* row, const int64_t* ptr,
-                                                           const int32_t* par, const double* blk, const uint8_t* fmask,
-                                                           float4* x4, int64_t nr, const int32_t* csub,
-                                                           const PcgScal* sc) {
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= nr) return;
-    const int64_t i = row[t];
-    if (stopped(sc, csub[i >> 6])) return;
-    double e0 = 0.0, e1 = 0.0, e2 = 0.0;
-    for (int64_t k = ptr[t]; k < ptr[t + 1]; ++k) {
-        const double* B = blk + 9 * k;
-        const int64_t c = par[k];
-        const double c0 = ec[3 * c], c1 = ec[3 * c + 1], c2 = ec[3 * c + 2];
-        e0 += B[0] * c0 + B[1] * c1 + B[2] * c2;
-        e1 += B[3] * c0 + B[4] * c1 + B[5] * c2;
-        e2 += B[6] * c0 + B[7] * c1 + B[8] * c2;
-    }
-    const uint8_t m = fmask[i];
-    float4 v = x4[i];
-    if (m & 1) v.x = (float)((double)v.x + e0);
-    if (m & 2) v.y = (float)((double)v.y + e1);
-    if (m & 4) v.z = (float)((double)v.z + e2);
-    x4[i] = v;
+    masked_add(xf, i, fmask[i], e0, e1, e2);
 }
 
 // ... and b_c += mask_c (B^T r_f) per coarse node that receives one (after k_restrict).
@@ -2392,8 +2317,7 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
             L.minv32.upload(m32);
         }
         if (l == nlev - 1 && nlev > 1 && opt.smoother >= 3) {
-            // the V-cycle copy's storage type of this level (vc_type once the level is up)
-            const int vt = (!vc32 || L.tbl) ? kVal64 : L.val8.p ? kValQ8 : L.val16.p ? kValH16 : kVal32;
+            const int vt = vc_type(l);  // (the level's value buffers are uploaded by now)
             // band mode (locally refined fine level): sweep only the nodes this level
             // adds to level l - 1 (reference positions past nnodes[l - 1]) and their neighbours --
             // elsewhere the stencils are level l - 1's, which the V-cycle smooths next -- when that
@@ -2822,6 +2746,57 @@ MgpisDevice::~MgpisDevice() {
     if (stream) (void)hipStreamDestroy(stream);
 }
 
+namespace {
+// ---- launch dispatch: the one place where a runtime choice of storage becomes a C++ type.  Each
+// helper calls the generic callable f with a tag that carries the type; the static exclusions
+// (which combinations have a kernel) stay with the caller as if constexpr.
+template <typename T>
+struct Tag {
+    using type = T;
+};
+template <typename TagT>
+using tag_t = typename TagT::type;
+
+// storage type of streamed operator values (ValType)
+template <typename F>
+void with_val_type(int vt, F&& f) {
+    if (vt == kValQ8) f(Tag<uint8_t>{});
+    else if (vt == kValH16) f(Tag<uint16_t>{});
+    else if (vt == kVal32) f(Tag<float>{});
+    else f(Tag<double>{});
+}
+
+// column type: 16-bit offsets from the row node where the level or colour copy has them (col16)
+template <typename F>
+void with_col_type(bool col16, F&& f) {
+    if (col16) f(Tag<int16_t>{});
+    else f(Tag<int32_t>{});
+}
+
+// type of the smoother's inverse: fp32 on levels whose V-cycle copy is reduced precision
+template <typename F>
+void with_inv_type(bool fp32, F&& f) {
+    if (fp32) f(Tag<float>{});
+    else f(Tag<double>{});
+}
+template <typename MT>
+const MT* level_minv(const LevelDev& L) {
+    if constexpr (std::is_same_v<MT, float>) return L.minv32.p;
+    else return L.minv.p;
+}
+
+// the smoother's first sweep x = omega M b as the <BJ, SETD, MT> arguments of k_jac0 and of the
+// restriction's fused sweep: Chebyshev (block inverse, sets d), block Jacobi, point Jacobi
+template <typename F>
+void with_first_sweep(bool cheb, bool bj, bool inv32, F&& f) {
+    with_inv_type(inv32, [&](auto tm) {
+        if (cheb) f(std::true_type{}, std::true_type{}, tm);
+        else if (bj) f(std::true_type{}, std::false_type{}, tm);
+        else f(std::false_type{}, std::false_type{}, tm);
+    });
+}
+}  // namespace
+
 // lambda_max(M K) per subdomain by 24 power iterations (all subdomains of the batch at once).
 void MgpisDevice::estimate_lmax(int l) {
     LevelDev& L = lev[l];
@@ -2850,11 +2825,12 @@ void MgpisDevice::estimate_lmax(int l) {
         }
     };
     auto apply_m = [&](const double* x) {
-        if (vc_type(l) != kVal64) {  // the smoother's own (fp32) inverse
-            if (bj) hipLaunchKernelGGL((k_apply_m<true, float>), dim3(nb), dim3(kBlock), 0, stream, x, L.minv32.p, w.p, partial.p, L.nn);
-            else hipLaunchKernelGGL((k_apply_m<false, float>), dim3(nb), dim3(kBlock), 0, stream, x, L.minv32.p, w.p, partial.p, L.nn);
-        } else if (bj) hipLaunchKernelGGL((k_apply_m<true>), dim3(nb), dim3(kBlock), 0, stream, x, L.minv.p, w.p, partial.p, L.nn);
-        else hipLaunchKernelGGL((k_apply_m<false>), dim3(nb), dim3(kBlock), 0, stream, x, L.minv.p, w.p, partial.p, L.nn);
+        with_inv_type(vc_type(l) != kVal64, [&](auto tm) {  // the smoother's own inverse (fp32 on reduced levels)
+            using MT = tag_t<decltype(tm)>;
+            const MT* m = level_minv<MT>(L);
+            if (bj) hipLaunchKernelGGL((k_apply_m<true, MT>), dim3(nb), dim3(kBlock), 0, stream, x, m, w.p, partial.p, L.nn);
+            else hipLaunchKernelGGL((k_apply_m<false, MT>), dim3(nb), dim3(kBlock), 0, stream, x, m, w.p, partial.p, L.nn);
+        });
     };
     apply_m(v.p);
     norms();
@@ -2898,96 +2874,71 @@ SellArgs level_args(const LevelDev& L) {
 // streamed in storage type vt (kVal64 / kVal32 / kValH16 / kValQ8)
 template <int MODE, bool BJ, bool DOT>
 void launch_sell(int vt, const SellArgs& a, hipStream_t s) {
-    const int grid = ceil_div(a.nch, 4);
+    const dim3 grid(ceil_div(a.nch, 4));
     constexpr int V = default_variant(MODE);
-    using I16 = int16_t;
+    // the V-cycle's sweep and residual: only they have the fp32 iterate copy and the row-split kernel
+    constexpr bool VC = MODE == kResid || MODE == kJac;
     // small levels: the row-split kernel (DDPCA_SPLIT_CHUNKS = the largest level it takes, in chunks)
     // (read per launch: launches are captured into graphs once per handle, and tests switch it)
     const char* esp = std::getenv("DDPCA_SPLIT_CHUNKS");
     const int64_t split_max = esp ? std::atoll(esp) : 2048;
-    if constexpr (MODE == kResid || MODE == kJac) {
-        if (a.x4) {
-            // a block-Jacobi level's fp32 iterate copy (LevelDev::x4a): the constructor enables it
-            // on levels with 16-bit columns and streamed values only
-            if (a.tab || !a.col16) throw ApiError(DDPCA_ESTATE, "fp32 iterate copy needs 16-bit columns and streamed values");
-            if (!DOT && a.nch <= split_max) {
-                const dim3 gs((unsigned)a.nch);
-                if (vt == kValQ8) hipLaunchKernelGGL((k_sell_split<MODE, BJ, uint8_t, I16, true>), gs, dim3(kBlock), 0, s, a);
-                else if (vt == kValH16) hipLaunchKernelGGL((k_sell_split<MODE, BJ, uint16_t, I16, true>), gs, dim3(kBlock), 0, s, a);
-                else if (vt == kVal32) hipLaunchKernelGGL((k_sell_split<MODE, BJ, float, I16, true>), gs, dim3(kBlock), 0, s, a);
-                else hipLaunchKernelGGL((k_sell_split<MODE, BJ, double, I16, true>), gs, dim3(kBlock), 0, s, a);
+    // a block-Jacobi level's fp32 iterate copy (LevelDev::x4a): the constructor enables it
+    // on levels with 16-bit columns and streamed values only
+    const bool x4 = VC && a.x4;
+    if (x4 && (a.tab || !a.col16)) throw ApiError(DDPCA_ESTATE, "fp32 iterate copy needs 16-bit columns and streamed values");
+    if (a.tab) {  // table mode: fp64 table, 32-bit columns
+        hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, V, true>), grid, dim3(kBlock), 0, s, a, a.tab);
+        return;
+    }
+    auto launch = [&](auto tv, auto tc, auto tx4) {
+        using T = tag_t<decltype(tv)>;
+        using CT = tag_t<decltype(tc)>;
+        constexpr bool X4 = decltype(tx4)::value;
+        // (V-cycle modes only: y = Kx keeps the slot order the table mode reproduces bit for bit)
+        if constexpr (VC && !DOT) {
+            if (a.nch <= split_max) {
+                hipLaunchKernelGGL((k_sell_split<MODE, BJ, T, CT, X4>), dim3((unsigned)a.nch), dim3(kBlock), 0, s, a);
                 return;
             }
-            if (vt == kValQ8) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint8_t, V, false, I16, true>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-            else if (vt == kValH16) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint16_t, V, false, I16, true>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-            else if (vt == kVal32) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, float, V, false, I16, true>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-            else hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, V, false, I16, true>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-            return;
         }
-    }
-    // (V-cycle modes only: y = Kx keeps the slot order the table mode reproduces bit for bit)
-    if constexpr (!DOT && (MODE == kResid || MODE == kJac)) {
-        if (!a.tab && a.nch <= split_max) {
-            const dim3 gs((unsigned)a.nch);
-            if (a.col16) {
-                if (vt == kValQ8) hipLaunchKernelGGL((k_sell_split<MODE, BJ, uint8_t, I16>), gs, dim3(kBlock), 0, s, a);
-                else if (vt == kValH16) hipLaunchKernelGGL((k_sell_split<MODE, BJ, uint16_t, I16>), gs, dim3(kBlock), 0, s, a);
-                else if (vt == kVal32) hipLaunchKernelGGL((k_sell_split<MODE, BJ, float, I16>), gs, dim3(kBlock), 0, s, a);
-                else hipLaunchKernelGGL((k_sell_split<MODE, BJ, double, I16>), gs, dim3(kBlock), 0, s, a);
-            } else if (vt == kValQ8) hipLaunchKernelGGL((k_sell_split<MODE, BJ, uint8_t, int32_t>), gs, dim3(kBlock), 0, s, a);
-            else if (vt == kValH16) hipLaunchKernelGGL((k_sell_split<MODE, BJ, uint16_t, int32_t>), gs, dim3(kBlock), 0, s, a);
-            else if (vt == kVal32) hipLaunchKernelGGL((k_sell_split<MODE, BJ, float, int32_t>), gs, dim3(kBlock), 0, s, a);
-            else hipLaunchKernelGGL((k_sell_split<MODE, BJ, double, int32_t>), gs, dim3(kBlock), 0, s, a);
-            return;
+        hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, T, V, false, CT, X4>), grid, dim3(kBlock), 0, s, a, a.tab);
+    };
+    with_val_type(vt, [&](auto tv) {
+        if constexpr (VC) {
+            if (x4) {
+                launch(tv, Tag<int16_t>{}, std::true_type{});
+                return;
+            }
         }
-    }
-    if (a.tab) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, V, true>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-    else if (a.col16) {
-        if (vt == kValQ8) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint8_t, V, false, I16>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-        else if (vt == kValH16) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint16_t, V, false, I16>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-        else if (vt == kVal32) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, float, V, false, I16>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-        else hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, V, false, I16>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-    } else if (vt == kValQ8) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint8_t>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-    else if (vt == kValH16) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint16_t>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-    else if (vt == kVal32) hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, float>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
-    else hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double>), dim3(grid), dim3(kBlock), 0, s, a, a.tab);
+        with_col_type(a.col16 != nullptr, [&](auto tc) { launch(tv, tc, std::false_type{}); });
+    });
 }
 
+// one smoothing sweep of the V-cycle: Chebyshev, block Jacobi or point Jacobi, with or without
+// the partials of the dot product
+void launch_sweep(bool cheb, bool bj, bool dot, int vt, const SellArgs& a, hipStream_t s) {
+    auto run = [&](auto tdot) {
+        constexpr bool DOT = decltype(tdot)::value;
+        if (cheb) launch_sell<kCheb, true, DOT>(vt, a, s);
+        else if (bj) launch_sell<kJac, true, DOT>(vt, a, s);
+        else launch_sell<kJac, false, DOT>(vt, a, s);
+    };
+    if (dot) run(std::true_type{});
+    else run(std::false_type{});
+}
+
+// the same with the loop variant chosen at run time (bench_spmv): 32-bit columns, streamed values
 template <int MODE, bool BJ, bool DOT>
 void launch_loop(int loop, int vt, const SellArgs& a, int grid, hipStream_t s) {
-    if (vt == kValQ8) {
+    with_val_type(vt, [&](auto tv) {
+        using T = tag_t<decltype(tv)>;
         switch (loop) {
-            case 0: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint8_t, 0>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            case 1: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint8_t, 1>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            case 2: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint8_t, 2>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            default: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint8_t, 3>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
+            case 0: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, T, 0>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
+            case 1: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, T, 1>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
+            case 2: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, T, 2>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
+            default: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, T, 3>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
         }
-        return;
-    }
-    if (vt == kValH16) {
-        switch (loop) {
-            case 0: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint16_t, 0>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            case 1: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint16_t, 1>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            case 2: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint16_t, 2>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            default: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, uint16_t, 3>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-        }
-        return;
-    }
-    if (vt == kVal32) {
-        switch (loop) {
-            case 0: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, float, 0>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            case 1: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, float, 1>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            case 2: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, float, 2>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-            default: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, float, 3>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-        }
-        return;
-    }
-    switch (loop) {
-        case 0: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, 0>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-        case 1: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, 1>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-        case 2: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, 2>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-        default: hipLaunchKernelGGL((k_sell<MODE, BJ, DOT, double, 3>), dim3(grid), dim3(kBlock), 0, s, a, a.tab); break;
-    }
+    });
 }
 }  // namespace
 
@@ -3047,15 +2998,71 @@ void MgpisDevice::rot_restrict(int l, const double* rf, double* bc, const PcgSca
                        F.rotc_ptr.p, F.rotc_kid.p, F.rotc_blk.p, lev[l - 1].mask.p, bc, F.nrotc, lev[l - 1].csub.p, scp);
 }
 
-void MgpisDevice::rot_prolong(int l, const double* ec, double* xf, const PcgScal* scp, float4* xf4) {
+void MgpisDevice::prolong_level(int l, const double* ec, double* xf, float4* xf4, const PcgScal* scp) {
     const LevelDev& F = lev[l];
-    if (!F.nrot) return;
-    if (xf4)  // the level's fp32 iterate copy (LevelDev::x4a)
-        hipLaunchKernelGGL(k_prolong_rot_x4, dim3(ceil_div(F.nrot, kBlock)), dim3(kBlock), 0, stream, ec, F.rot_row.p,
-                           F.rot_ptr.p, F.rot_par.p, F.rot_blk.p, F.mask.p, xf4, F.nrot, F.csub.p, scp);
+    const dim3 grid(ceil_div(F.nn, kBlock)), block(kBlock);
+    auto into = [&](auto* x) {  // x: the fp64 iterate, or the fp32 copy that takes the correction instead
+        using XT = std::remove_pointer_t<decltype(x)>;
+        if (F.lat)
+            hipLaunchKernelGGL(k_prolong_lat<XT>, grid, block, 0, stream, ec, F.ppk.p, F.pstr.p, F.mask.p, x, F.nn, F.csub.p, scp);
+        else if (F.uw)
+            hipLaunchKernelGGL((k_prolong<true, XT>), grid, block, 0, stream, ec, F.ppar.p, F.pw.p, F.mask.p, x, F.nn, F.csub.p, scp);
+        else
+            hipLaunchKernelGGL((k_prolong<false, XT>), grid, block, 0, stream, ec, F.ppar.p, F.pw.p, F.mask.p, x, F.nn, F.csub.p, scp);
+        if (F.nrot)  // the block entries' part
+            hipLaunchKernelGGL(k_prolong_rot<XT>, dim3(ceil_div(F.nrot, kBlock)), block, 0, stream, ec, F.rot_row.p,
+                               F.rot_ptr.p, F.rot_par.p, F.rot_blk.p, F.mask.p, x, F.nrot, F.csub.p, scp);
+    };
+    if (xf4) into(xf4);
+    else into(xf);
+}
+
+void MgpisDevice::first_sweep(int l, const double* b, const double* cf, double* x, float4* x4, const PcgScal* scp) {
+    const LevelDev& L = lev[l];
+    with_first_sweep(opt.smoother == 2, opt.smoother >= 1, vc_type(l) != kVal64, [&](auto bj, auto setd, auto tm) {
+        using MT = tag_t<decltype(tm)>;
+        constexpr bool BJ = decltype(bj)::value, SETD = decltype(setd)::value;
+        hipLaunchKernelGGL((k_jac0<BJ, SETD, MT>), dim3(ceil_div(L.nn, kBlock)), dim3(kBlock), 0, stream, b,
+                           level_minv<MT>(L), cf, x, SETD ? L.d.p : nullptr, L.nn, L.csub.p, scp, x4);
+    });
+}
+
+void MgpisDevice::coarse_solve(const double* b, double* x, const PcgScal* scp) {
+    const LevelDev& C = lev[clev];
+    const dim3 grid(ceil_div(3 * C.nn, 4));
+    if (ainv32.p)
+        hipLaunchKernelGGL(k_coarse<float>, grid, dim3(kBlock), 0, stream, ainv32.p, aoff.p, c_noff.p, c_n.p, c_ld.p, b, x,
+                           3 * C.nn, C.csub.p, scp);
     else
-        hipLaunchKernelGGL(k_prolong_rot, dim3(ceil_div(F.nrot, kBlock)), dim3(kBlock), 0, stream, ec, F.rot_row.p,
-                           F.rot_ptr.p, F.rot_par.p, F.rot_blk.p, F.mask.p, xf, F.nrot, F.csub.p, scp);
+        hipLaunchKernelGGL(k_coarse<double>, grid, dim3(kBlock), 0, stream, ainv.p, aoff.p, c_noff.p, c_n.p, c_ld.p, b, x,
+                           3 * C.nn, C.csub.p, scp);
+}
+
+void MgpisDevice::restrict_into(int c, const float4* rf4, double* xc, float4* xc4, const PcgScal* scp) {
+    const LevelDev& F = lev[c + 1];
+    const LevelDev& C = lev[c];
+    const int grid = ceil_div(C.nn, kBlock);
+    const double* cf = c > 0 ? lev[c].coef.p : nullptr;  // the first sweep's (c1, c2)
+    auto plain = [&](const float4* r4) {
+        launch_restrict<false, false, false, double>(F, grid, stream, F.r.p, C.mask.p, C.b.p, nullptr, nullptr, nullptr,
+                                                     nullptr, C.nn, C.csub.p, scp, r4);
+    };
+    if (F.nrot) {
+        // block transfer entries: plain restriction, the blocks' B^T part, then the first
+        // coarse sweep x_c = omega M b_c that k_restrict otherwise fuses
+        plain(nullptr);
+        rot_restrict(c + 1, F.r.p, C.b.p, scp);
+        if (c != clev) first_sweep(c, C.b.p, cf, xc, xc4, scp);
+    } else if (c == clev) {
+        plain(rf4);
+    } else {
+        with_first_sweep(opt.smoother == 2, opt.smoother >= 1, vc_type(c) != kVal64, [&](auto bj, auto setd, auto tm) {
+            using MT = tag_t<decltype(tm)>;
+            constexpr bool BJ = decltype(bj)::value, SETD = decltype(setd)::value;
+            launch_restrict<true, BJ, SETD, MT>(F, grid, stream, F.r.p, C.mask.p, C.b.p, xc, SETD ? C.d.p : nullptr,
+                                                level_minv<MT>(C), cf, C.nn, C.csub.p, scp, rf4, xc4);
+        });
+    }
 }
 
 void MgpisDevice::spmv(int level, const double* x, double* y, bool vc_op) {
@@ -3101,30 +3108,30 @@ double MgpisDevice::bench_spmv(int variant, int reps) {
         DDPCA_HIP(hipMemcpy2DAsync(x4.p, 32, xs.p, 24, 24, L.nn, hipMemcpyDeviceToDevice, stream));
         a.x = x4.p;
     }
+    auto table_variant = [&](auto v) {  // y = Kx from the table, diagnostic loop variant v
+        hipLaunchKernelGGL((k_sell<kSpmv, false, false, double, decltype(v)::value, true>), dim3(grid), dim3(kBlock), 0,
+                           stream, a, a.tab);
+    };
+    auto in_mode = [&](auto m, auto bj, auto dot) {
+        constexpr int MODE = decltype(m)::value;
+        constexpr bool BJ = decltype(bj)::value, DOT = decltype(dot)::value;
+        if (a.tab) launch_sell<MODE, BJ, DOT>(kVal64, a, stream);  // table mode: one loop variant
+        else launch_loop<MODE, BJ, DOT>(loop, vt, a, grid, stream);
+    };
+    using std::integral_constant;
     auto launch = [&]() {
         if (a.tab && mode == 0 && tloop != 1) {
-#define TBL_V(v) hipLaunchKernelGGL((k_sell<kSpmv, false, false, double, v, true>), dim3(grid), dim3(kBlock), 0, stream, a, a.tab)
             switch (tloop) {
-                case 0: TBL_V(0); break;
-                case 3: TBL_V(3); break;
-                case 4: TBL_V(4); break;
-                case 5: TBL_V(5); break;
-                default: TBL_V(2); break;
+                case 0: table_variant(integral_constant<int, 0>{}); break;
+                case 3: table_variant(integral_constant<int, 3>{}); break;
+                case 4: table_variant(integral_constant<int, 4>{}); break;
+                case 5: table_variant(integral_constant<int, 5>{}); break;
+                default: table_variant(integral_constant<int, 2>{}); break;
             }
-#undef TBL_V
-            return;
-        }
-        if (a.tab) {  // table mode: one loop variant
-            if (mode == 0) launch_sell<kSpmv, false, false>(kVal64, a, stream);
-            else if (mode == 1) launch_sell<kPcg, false, true>(kVal64, a, stream);
-            else if (mode == 2) launch_sell<kResid, false, false>(kVal64, a, stream);
-            else launch_sell<kCheb, true, false>(kVal64, a, stream);
-            return;
-        }
-        if (mode == 0) launch_loop<kSpmv, false, false>(loop, vt, a, grid, stream);
-        else if (mode == 1) launch_loop<kPcg, false, true>(loop, vt, a, grid, stream);
-        else if (mode == 2) launch_loop<kResid, false, false>(loop, vt, a, grid, stream);
-        else launch_loop<kCheb, true, false>(loop, vt, a, grid, stream);
+        } else if (mode == 0) in_mode(integral_constant<int, kSpmv>{}, std::false_type{}, std::false_type{});
+        else if (mode == 1) in_mode(integral_constant<int, kPcg>{}, std::false_type{}, std::true_type{});
+        else if (mode == 2) in_mode(integral_constant<int, kResid>{}, std::false_type{}, std::false_type{});
+        else in_mode(integral_constant<int, kCheb>{}, std::true_type{}, std::false_type{});
     };
     launch();
     DDPCA_HIP(hipEventRecord(ev_k0, stream));
@@ -3137,35 +3144,15 @@ double MgpisDevice::bench_spmv(int variant, int reps) {
 }
 
 namespace {
-// one k_gs launch: phase ph over colour k's chunks (k < 0: every chunk)
-template <int PH, bool DOT, typename T>
-void launch_gs_t(const GsArgs& a, bool c16, hipStream_t st) {  // c16: 16-bit column offsets, else int32 columns
-    if (a.x4) {
-        if (c16) hipLaunchKernelGGL((k_gs<PH, DOT, T, int16_t, true>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-        else hipLaunchKernelGGL((k_gs<PH, DOT, T, int32_t, true>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-        return;
-    }
-    if (c16) hipLaunchKernelGGL((k_gs<PH, DOT, T, int16_t>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-    else hipLaunchKernelGGL((k_gs<PH, DOT, T, int32_t>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
+// the colour copy the sweeps stream: its storage type and values (GsFine holds exactly one)
+std::pair<int, const void*> gs_values(const GsFine& G) {
+    if (G.val8.p) return {kValQ8, G.val8.p};
+    if (G.val16.p) return {kValH16, G.val16.p};
+    if (G.val32.p) return {kVal32, G.val32.p};
+    return {kVal64, G.val64.p};
 }
 
-template <int PH, bool DOT, typename T>
-void launch_gs_ssor_t(const GsArgs& a, bool c16, hipStream_t st) {
-    if (a.x4) {
-        if (c16) hipLaunchKernelGGL((k_gs_ssor<PH, DOT, T, int16_t, true>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-        else hipLaunchKernelGGL((k_gs_ssor<PH, DOT, T, int32_t, true>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-        return;
-    }
-    if (c16) hipLaunchKernelGGL((k_gs_ssor<PH, DOT, T, int16_t>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-    else hipLaunchKernelGGL((k_gs_ssor<PH, DOT, T, int32_t>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-}
-
-template <int PH, typename T>
-void launch_gs_aux_t(const GsArgs& a, bool c16, hipStream_t st) {
-    if (c16) hipLaunchKernelGGL((k_gs_aux<PH, T, int16_t>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-    else hipLaunchKernelGGL((k_gs_aux<PH, T, int32_t>), dim3((unsigned)a.n), dim3(kWave), 0, st, a);
-}
-
+// one colour-sweep launch: phase PH (k_gs, 6..10 k_gs_ssor) over the chunks k selects.
 // k >= 0: colour k; k = -1: every colour chunk (the residual); band mode: k = -2 the ring group,
 // k = -3 the ring and far groups (PH 3..5 run k_gs_aux)
 template <int PH, bool DOT>
@@ -3205,36 +3192,34 @@ void launch_gs(const MgpisDevice& D, int k, double* x, const double* b, double* 
     a.x4 = reinterpret_cast<float4*>(G.x4.p);
     a.r4 = reinterpret_cast<float4*>(G.r4.p);
     a.w = G.w.p;
-    const bool c16 = G.col16.p != nullptr;
-    if constexpr (PH >= 6) {  // SSOR phases: the reduced-precision copies' chunk-ordered inverses
-        if (!G.minvc.p) throw ApiError(DDPCA_ESTATE, "colour SSOR needs a reduced-precision V-cycle copy (precond_fp32 >= 1)");
-        a.minv = F.minv32.p;
-        if (G.val8.p) a.val = G.val8.p, launch_gs_ssor_t<PH, DOT, uint8_t>(a, c16, D.stream);
-        else if (G.val16.p) a.val = G.val16.p, launch_gs_ssor_t<PH, DOT, uint16_t>(a, c16, D.stream);
-        else a.val = G.val32.p, launch_gs_ssor_t<PH, DOT, float>(a, c16, D.stream);
-        return;
-    }
-    if (G.val8.p) {
-        a.val = G.val8.p;
-        a.minv = F.minv32.p;
-        if constexpr (PH >= 3) launch_gs_aux_t<PH, uint8_t>(a, c16, D.stream);
-        else launch_gs_t<PH, DOT, uint8_t>(a, c16, D.stream);
-    } else if (G.val16.p) {
-        a.val = G.val16.p;
-        a.minv = F.minv32.p;
-        if constexpr (PH >= 3) launch_gs_aux_t<PH, uint16_t>(a, c16, D.stream);
-        else launch_gs_t<PH, DOT, uint16_t>(a, c16, D.stream);
-    } else if (G.val32.p) {
-        a.val = G.val32.p;
-        a.minv = F.minv32.p;
-        if constexpr (PH >= 3) launch_gs_aux_t<PH, float>(a, c16, D.stream);
-        else launch_gs_t<PH, DOT, float>(a, c16, D.stream);
-    } else {
-        a.val = G.val64.p;
-        a.minv = F.minv.p;
-        if constexpr (PH >= 3) launch_gs_aux_t<PH, double>(a, c16, D.stream);
-        else launch_gs_t<PH, DOT, double>(a, c16, D.stream);
-    }
+    const auto [vt, val] = gs_values(G);
+    a.val = val;
+    if (vt != kVal64) a.minv = F.minv32.p;
+    else a.minv = F.minv.p;
+    // SSOR phases: the reduced-precision copies' chunk-ordered inverses
+    if (PH >= 6 && (!G.minvc.p || vt == kVal64))
+        throw ApiError(DDPCA_ESTATE, "colour SSOR needs a reduced-precision V-cycle copy (precond_fp32 >= 1)");
+    const dim3 grid((unsigned)a.n);
+    with_val_type(vt, [&](auto tv) {
+        with_col_type(G.col16.p != nullptr, [&](auto tc) {
+            using T = tag_t<decltype(tv)>;
+            using CT = tag_t<decltype(tc)>;
+            if constexpr (PH >= 6) {
+                if constexpr (!std::is_same_v<T, double>) {
+                    if (a.x4) hipLaunchKernelGGL((k_gs_ssor<PH, DOT, T, CT, true>), grid, dim3(kWave), 0, D.stream, a);
+                    else hipLaunchKernelGGL((k_gs_ssor<PH, DOT, T, CT>), grid, dim3(kWave), 0, D.stream, a);
+                    return;
+                }
+            }
+            // (no else: as before, the code object also carries k_gs_aux<6..10>, which nothing launches)
+            if constexpr (PH >= 3) {  // the band mode's ring / far groups
+                hipLaunchKernelGGL((k_gs_aux<PH, T, CT>), grid, dim3(kWave), 0, D.stream, a);
+            } else {
+                if (a.x4) hipLaunchKernelGGL((k_gs<PH, DOT, T, CT, true>), grid, dim3(kWave), 0, D.stream, a);
+                else hipLaunchKernelGGL((k_gs<PH, DOT, T, CT>), grid, dim3(kWave), 0, D.stream, a);
+            }
+        });
+    });
 }
 }  // namespace
 
@@ -3248,10 +3233,7 @@ void MgpisDevice::vcycle(const double* rin, double* zout, bool dot) {
     const PcgScal* scp = sc_cur_ ? sc_cur_ : sc.p;
     const int cl = clev;  // the exact dense solve; levels below it are not visited
     if (Lf == cl) {
-        if (ainv32.p) hipLaunchKernelGGL(k_coarse<float>, dim3(ceil_div(3 * lev[cl].nn, 4)), dim3(kBlock), 0, stream, ainv32.p, aoff.p, c_noff.p,
-                           c_n.p, c_ld.p, rin, zout, 3 * lev[cl].nn, lev[cl].csub.p, scp);
-        else hipLaunchKernelGGL(k_coarse<double>, dim3(ceil_div(3 * lev[cl].nn, 4)), dim3(kBlock), 0, stream, ainv.p, aoff.p, c_noff.p,
-                           c_n.p, c_ld.p, rin, zout, 3 * lev[cl].nn, lev[cl].csub.p, scp);
+        coarse_solve(rin, zout, scp);
         if (dot)
             hipLaunchKernelGGL(k_dot, dim3(ceil_div(lev[cl].nn, kBlock)), dim3(kBlock), 0, stream, rin, zout, partial.p,
                                lev[cl].nn, lev[cl].csub.p, scp);
@@ -3275,7 +3257,7 @@ void MgpisDevice::vcycle(const double* rin, double* zout, bool dot) {
     // smoothing sweeps on level l from the current iterate (first: jac0/restrict already did sweep 0);
     // out64: the last of them is the level's output (fp64 also on an fp32-copy level)
     auto smooth = [&](int l, int first, int count, bool last_dot, bool out64) {
-        const int f32 = vc_type(l);
+        const int vt = vc_type(l);
         for (int s = first; s < first + count; ++s) {
             SellArgs a = vc_level_args(*this, l);
             a.sc = scp;
@@ -3291,17 +3273,8 @@ void MgpisDevice::vcycle(const double* rin, double* zout, bool dot) {
                 a.xo = fin ? oth[l] : nullptr;
             }
             const bool d = last_dot && s == first + count - 1;
-            if (cheb) {
-                a.p = lev[l].d.p;
-                if (d) launch_sell<kCheb, true, true>(f32, a, stream);
-                else launch_sell<kCheb, true, false>(f32, a, stream);
-            } else if (bj) {
-                if (d) launch_sell<kJac, true, true>(f32, a, stream);
-                else launch_sell<kJac, true, false>(f32, a, stream);
-            } else {
-                if (d) launch_sell<kJac, false, true>(f32, a, stream);
-                else launch_sell<kJac, false, false>(f32, a, stream);
-            }
+            if (cheb) a.p = lev[l].d.p;
+            launch_sweep(cheb, bj, d, vt, a, stream);
             std::swap(cur[l], oth[l]);
             std::swap(cur4[l], oth4[l]);
         }
@@ -3323,16 +3296,7 @@ void MgpisDevice::vcycle(const double* rin, double* zout, bool dot) {
         launch_gs<1, false>(*this, -1, zout, nullptr, lev[Lf].r.p, scp, nullptr);
         if (gs.band) launch_gs<3, false>(*this, -2, zout, rin, lev[Lf].r.p, scp, nullptr);
     } else {
-        const LevelDev& F = lev[Lf];
-        const int grid = ceil_div(F.nn, kBlock);
-        if (vc_type(Lf) != kVal64) {
-            const float* m = F.minv32.p;
-            if (cheb) hipLaunchKernelGGL((k_jac0<true, true, float>), dim3(grid), dim3(kBlock), 0, stream, rin, m, coef(Lf, 0), cur[Lf], F.d.p, F.nn, F.csub.p, scp, cur4[Lf]);
-            else if (bj) hipLaunchKernelGGL((k_jac0<true, false, float>), dim3(grid), dim3(kBlock), 0, stream, rin, m, coef(Lf, 0), cur[Lf], nullptr, F.nn, F.csub.p, scp, cur4[Lf]);
-            else hipLaunchKernelGGL((k_jac0<false, false, float>), dim3(grid), dim3(kBlock), 0, stream, rin, m, coef(Lf, 0), cur[Lf], nullptr, F.nn, F.csub.p, scp, cur4[Lf]);
-        } else if (cheb) hipLaunchKernelGGL((k_jac0<true, true>), dim3(grid), dim3(kBlock), 0, stream, rin, F.minv.p, coef(Lf, 0), cur[Lf], F.d.p, F.nn, F.csub.p, scp, cur4[Lf]);
-        else if (bj) hipLaunchKernelGGL((k_jac0<true, false>), dim3(grid), dim3(kBlock), 0, stream, rin, F.minv.p, coef(Lf, 0), cur[Lf], nullptr, F.nn, F.csub.p, scp, cur4[Lf]);
-        else hipLaunchKernelGGL((k_jac0<false, false>), dim3(grid), dim3(kBlock), 0, stream, rin, F.minv.p, coef(Lf, 0), cur[Lf], nullptr, F.nn, F.csub.p, scp, cur4[Lf]);
+        first_sweep(Lf, rin, coef(Lf, 0), cur[Lf], cur4[Lf], scp);
     }
     for (int l = Lf; l >= cl + 1; --l) {
         if (!(gsf && l == Lf)) {
@@ -3345,71 +3309,17 @@ void MgpisDevice::vcycle(const double* rin, double* zout, bool dot) {
             a.y = lev[l].r.p;
             launch_sell<kResid, false, false>(vc_type(l), a, stream);
         }
-        const int c = l - 1;
-        const LevelDev& F = lev[l];
-        const LevelDev& C = lev[c];
-        const int grid = ceil_div(C.nn, kBlock);
-        const double* cf = c > 0 ? coef(c, 0) : nullptr;
-        if (F.nrot) {
-            // block transfer entries: plain restriction, the blocks' B^T part, then the first
-            // coarse sweep x_c = omega M b_c that k_restrict otherwise fuses
-            launch_restrict<false, false, false, double>(F, grid, stream, F.r.p, C.mask.p, C.b.p, nullptr, nullptr, nullptr, nullptr, C.nn, C.csub.p, scp);
-            rot_restrict(l, F.r.p, C.b.p, scp);
-            if (c != cl) {
-                const bool f32c = vc_type(c) != kVal64;
-                const float* m32 = C.minv32.p;
-                if (cheb && f32c) hipLaunchKernelGGL((k_jac0<true, true, float>), dim3(grid), dim3(kBlock), 0, stream, C.b.p, m32, cf, cur[c], C.d.p, C.nn, C.csub.p, scp, cur4[c]);
-                else if (bj && f32c) hipLaunchKernelGGL((k_jac0<true, false, float>), dim3(grid), dim3(kBlock), 0, stream, C.b.p, m32, cf, cur[c], nullptr, C.nn, C.csub.p, scp, cur4[c]);
-                else if (f32c) hipLaunchKernelGGL((k_jac0<false, false, float>), dim3(grid), dim3(kBlock), 0, stream, C.b.p, m32, cf, cur[c], nullptr, C.nn, C.csub.p, scp, cur4[c]);
-                else if (cheb) hipLaunchKernelGGL((k_jac0<true, true>), dim3(grid), dim3(kBlock), 0, stream, C.b.p, C.minv.p, cf, cur[c], C.d.p, C.nn, C.csub.p, scp, cur4[c]);
-                else if (bj) hipLaunchKernelGGL((k_jac0<true, false>), dim3(grid), dim3(kBlock), 0, stream, C.b.p, C.minv.p, cf, cur[c], nullptr, C.nn, C.csub.p, scp, cur4[c]);
-                else hipLaunchKernelGGL((k_jac0<false, false>), dim3(grid), dim3(kBlock), 0, stream, C.b.p, C.minv.p, cf, cur[c], nullptr, C.nn, C.csub.p, scp, cur4[c]);
-            }
-        } else {
-            // x4 mode: the colour sweeps' residual is the fp32 copy (GsFine::r4)
-            const float4* rf4 = gsf && l == Lf && gs.r4.p ? reinterpret_cast<const float4*>(gs.r4.p) : nullptr;
-            if (c == cl)
-                launch_restrict<false, false, false, double>(F, grid, stream, F.r.p, C.mask.p, C.b.p, nullptr, nullptr, nullptr, nullptr, C.nn, C.csub.p, scp, rf4);
-            else if (vc_type(c) != kVal64) {
-                const float* m = C.minv32.p;
-                if (cheb)
-                    launch_restrict<true, true, true, float>(F, grid, stream, F.r.p, C.mask.p, C.b.p, cur[c], C.d.p, m, cf, C.nn, C.csub.p, scp, rf4, cur4[c]);
-                else if (bj)
-                    launch_restrict<true, true, false, float>(F, grid, stream, F.r.p, C.mask.p, C.b.p, cur[c], nullptr, m, cf, C.nn, C.csub.p, scp, rf4, cur4[c]);
-                else
-                    launch_restrict<true, false, false, float>(F, grid, stream, F.r.p, C.mask.p, C.b.p, cur[c], nullptr, m, cf, C.nn, C.csub.p, scp, rf4, cur4[c]);
-            } else if (cheb)
-                launch_restrict<true, true, true, double>(F, grid, stream, F.r.p, C.mask.p, C.b.p, cur[c], C.d.p, C.minv.p, cf, C.nn, C.csub.p, scp, rf4, cur4[c]);
-            else if (bj)
-                launch_restrict<true, true, false, double>(F, grid, stream, F.r.p, C.mask.p, C.b.p, cur[c], nullptr, C.minv.p, cf, C.nn, C.csub.p, scp, rf4, cur4[c]);
-            else
-                launch_restrict<true, false, false, double>(F, grid, stream, F.r.p, C.mask.p, C.b.p, cur[c], nullptr, C.minv.p, cf, C.nn, C.csub.p, scp, rf4, cur4[c]);
-        }
+        // x4 mode: the colour sweeps' residual is the fp32 copy (GsFine::r4)
+        const float4* rf4 = gsf && l == Lf && gs.r4.p ? reinterpret_cast<const float4*>(gs.r4.p) : nullptr;
+        restrict_into(l - 1, rf4, cur[l - 1], cur4[l - 1], scp);
     }
-    if (ainv32.p) hipLaunchKernelGGL(k_coarse<float>, dim3(ceil_div(3 * lev[cl].nn, 4)), dim3(kBlock), 0, stream, ainv32.p, aoff.p, c_noff.p,
-                           c_n.p, c_ld.p, lev[cl].b.p, cur[cl], 3 * lev[cl].nn, lev[cl].csub.p, scp);
-        else hipLaunchKernelGGL(k_coarse<double>, dim3(ceil_div(3 * lev[cl].nn, 4)), dim3(kBlock), 0, stream, ainv.p, aoff.p, c_noff.p,
-                       c_n.p, c_ld.p, lev[cl].b.p, cur[cl], 3 * lev[cl].nn, lev[cl].csub.p, scp);
+    coarse_solve(lev[cl].b.p, cur[cl], scp);
     // ---- ascend
     for (int l = cl + 1; l <= Lf; ++l) {
-        const LevelDev& F = lev[l];
-        if (gsf && l == Lf && gs.x4.p)  // (x4 mode: lattice fine transfer, no block entries, GsFine::x4)
-            hipLaunchKernelGGL(k_prolong_lat_x4, dim3(ceil_div(F.nn, kBlock)), dim3(kBlock), 0, stream, cur[l - 1], F.ppk.p,
-                               F.pstr.p, F.mask.p, reinterpret_cast<float4*>(gs.x4.p), F.nn, F.csub.p, scp);
-        else if (cur4[l] && F.lat)  // a block-Jacobi level's fp32 copy (no block entries into it)
-            hipLaunchKernelGGL(k_prolong_lat_x4, dim3(ceil_div(F.nn, kBlock)), dim3(kBlock), 0, stream, cur[l - 1], F.ppk.p,
-                               F.pstr.p, F.mask.p, cur4[l], F.nn, F.csub.p, scp);
-        else if (cur4[l] && F.uw) hipLaunchKernelGGL(k_prolong_x4<true>, dim3(ceil_div(F.nn, kBlock)), dim3(kBlock), 0, stream, cur[l - 1],
-                                                F.ppar.p, F.pw.p, F.mask.p, cur4[l], F.nn, F.csub.p, scp);
-        else if (cur4[l]) hipLaunchKernelGGL(k_prolong_x4<false>, dim3(ceil_div(F.nn, kBlock)), dim3(kBlock), 0, stream, cur[l - 1],
-                                        F.ppar.p, F.pw.p, F.mask.p, cur4[l], F.nn, F.csub.p, scp);
-        else if (F.lat) hipLaunchKernelGGL(k_prolong_lat, dim3(ceil_div(F.nn, kBlock)), dim3(kBlock), 0, stream, cur[l - 1], F.ppk.p,
-                                      F.pstr.p, F.mask.p, cur[l], F.nn, F.csub.p, scp);
-        else if (F.uw) hipLaunchKernelGGL(k_prolong<true>, dim3(ceil_div(F.nn, kBlock)), dim3(kBlock), 0, stream, cur[l - 1], F.ppar.p, F.pw.p,
-                           F.mask.p, cur[l], F.nn, F.csub.p, scp);
-        else hipLaunchKernelGGL(k_prolong<false>, dim3(ceil_div(F.nn, kBlock)), dim3(kBlock), 0, stream, cur[l - 1], F.ppar.p, F.pw.p,
-                           F.mask.p, cur[l], F.nn, F.csub.p, scp);
-        rot_prolong(l, cur[l - 1], cur[l], scp, cur4[l]);
+        // x4 mode (GsFine::x4: lattice fine transfer, no block entries): into the colour sweeps'
+        // fp32 copy; a block-Jacobi level's fp32 copy likewise takes the correction
+        float4* x4 = gsf && l == Lf && gs.x4.p ? reinterpret_cast<float4*>(gs.x4.p) : cur4[l];
+        prolong_level(l, cur[l - 1], cur[l], x4, scp);
         if (ssor && l == Lf) {
             // colour SSOR after the coarse correction: forward, then backward with the dot partials
             for (int k = 0; k < gs.ncol; ++k) launch_gs<9, false>(*this, k, zout, rin, nullptr, scp, nullptr);

@@ -269,9 +269,8 @@ public:
     void vcycle(const double* r, double* z, bool dot);
     // b_{l-1} = realProl[l-1]^T r_l on every member (masked), batch nodal layouts of levels l, l-1
     void restrict_level(int l, const double* rf, double* bc);
-    // block (rotated-node) parts of the transfer from level l-1 to l: b_c += B^T r_f, x_f += B e_c
+    // block (rotated-node) part of the restriction from level l to l-1: b_c += B^T r_f
     void rot_restrict(int l, const double* rf, double* bc, const PcgScal* scp);
-    void rot_prolong(int l, const double* ec, double* xf, const PcgScal* scp, float4* xf4 = nullptr);
     // PCG over every subdomain of the batch; b in bs, result in xs (x0 = xs when warm).
     // begin() enqueues the setup, step() one graph replay (iters_per_graph iterations),
     // wait() paces replays on the host-mapped stop flags until every subdomain is done.
@@ -356,6 +355,16 @@ private:
     void build_graph(int prec);
     void enqueue_iteration(int prec, bool timed);
     void estimate_lmax(int level);
+    // ---- the V-cycle's launches (scp: the stop flags the cycle binds)
+    // x = omega M b on level l from a zero guess, into the level's fp32 iterate copy x4 when set
+    void first_sweep(int l, const double* b, const double* cf, double* x, float4* x4, const PcgScal* scp);
+    // x = A^-1 b on level clev (the packed dense inverses)
+    void coarse_solve(const double* b, double* x, const PcgScal* scp);
+    // b_c = R r_{c+1} (rf4: the fine residual's fp32 copy instead of lev[c+1].r) and, above clev,
+    // the first sweep on level c into xc / xc4, fused unless the transfer has block entries
+    void restrict_into(int c, const float4* rf4, double* xc, float4* xc4, const PcgScal* scp);
+    // x_l += P e_{l-1}, block entries (x_f += B e_c) included: into xf4, an fp32 iterate copy, when set
+    void prolong_level(int l, const double* ec, double* xf, float4* xf4, const PcgScal* scp);
 };
 
 // The other drivers of the MGPIS class surface (device_krylov.hip), on member 0 of a one-member

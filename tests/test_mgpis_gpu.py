@@ -189,8 +189,8 @@ def test_block_jacobi_fp32_iterate_copy_keeps_the_solution(ddpca, gpu, monkeypat
     gather it, and only the level's last sweep writes fp64.  The products and epilogues stay fp64:
     the V-cycle moves by the fp32 rounding of the iterates only, stays symmetric to that rounding,
     and PCG reaches the same ||r|| <= 1e-14 ||b|| within one more iteration.  general: the general
-    mesh's rotated support nodes (rotation block entries in the prolongation, k_prolong_rot_x4) and
-    explicit transfer lists (k_prolong_x4)."""
+    mesh's rotated support nodes (rotation block entries in the prolongation, k_prolong_rot<float4>) and
+    explicit transfer lists (k_prolong<UW, float4>)."""
     if mesh == "general":
         monkeypatch.setenv("DDPCA_LATTICE", "0")
         P = ddpca.headline_problem(gl=3, **ddpca.GENERAL_FEATURES).ESTABLISH()

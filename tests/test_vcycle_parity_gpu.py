@@ -20,15 +20,16 @@ Cases (vcycle_host.parity_cases): c1 headline gl 2 (partial last chunks), subdom
 storage, smoothers 0-3 x nu x omega x exact level 0 / L-1 / -1; c2 gl 3, smoothers 1 / 3, table mode 0 /
 2, lattice on / off; c3 the general mesh (band mode, rotation blocks, explicit lists); c4 the CSR
 drop-in on beam_s2 and the realProl drop-in on the rotated beam_s1 hierarchy; c5 precond_fp32 1-3 with
-smoothers 1 / 3 and colour SSOR at 1 (precond_fp32 = 4 stays pinned to 3 by test_mgpis_gpu.py).
+smoothers 1 / 3 and colour SSOR at 1 (precond_fp32 = 4 stays pinned to 3 by test_mgpis_gpu.py); c6 point
+Jacobi and Chebyshev at precond_fp32 1 / 3 (their first sweep and fused restriction with the fp32 inverse).
 
 The batched V-cycle -- several members per handle as MCONTACT builds it, per-member coefficients and
 done-member skipping -- and the batched PCG are held to the same restatement, member by member, in
 test_batch_parity_gpu.py (mgpis_gpu_batch_vcycle / mgpis_gpu_batch_solve).
 
 Measured device errors (MI355X, relative max-norm, every right-hand side): c1 6e-18 .. 1.1e-15, c2
-1.4e-17 .. 9.9e-16, c3 2.5e-17 .. 1.2e-15, c5 2.1e-17 .. 7.6e-16 (tolerance 1e-13); c4 CSR beam_s2 4.5e-12 ..
-1.4e-11 (floor 2.7e-12, tolerance 1.3e-10), rotated beam_s1 1.3e-15 .. 1.4e-13 (tolerance 2.4e-12 .. 5e-12).
+1.4e-17 .. 9.9e-16, c3 2.5e-17 .. 1.2e-15, c5 2.1e-17 .. 7.6e-16, c6 2.4e-17 .. 7.4e-16 (tolerance 1e-13);
+c4 CSR beam_s2 4.5e-12 .. 1.4e-11 (floor 2.7e-12, tolerance 1.3e-10), rotated beam_s1 1.3e-15 .. 1.4e-13 (tolerance 2.4e-12 .. 5e-12).
 PCG, one / two steps: 2.4e-16 .. 1.8e-15 (c1), 3.4e-16 .. 3.6e-15 (c3); the cap stops the device at exactly k
 iterations although a graph holds iters_per_graph of them.
 

@@ -609,6 +609,11 @@ def parity_cases():
             add("c5", "h2", tv, 1, 1, -1.7, 0, f32=f32)
             add("c5", "h2", tv, 3, 2, -1.7, 0, f32=f32)
         add("c5", "h2", tv, 4, 2, -1.7, 0, f32=1)
+    # point Jacobi and Chebyshev on reduced-precision levels: the first sweep and the restriction's fused
+    # sweep with the fp32 inverse under those two smoothers, and their sweeps over the fp32 / int8 copies
+    for s, om in ((0, 0.5), (2, -1.7)):
+        for f32 in (1, 3):
+            add("c6", "h2", 0, s, 2, om, 0, f32=f32)
     return out
 
 
