@@ -1161,14 +1161,15 @@ def mass_solve(systems: Sequence, b: np.ndarray, rtol: float = 1e-14, maxit: int
     """The ADMM loop's batched surface-mass Jacobi-PCG on its own (ddpca_mass_solve): systems = square
     scipy CSR matrices, b their right-hand sides concatenated.  Returns (x, iterations per system);
     a breakdown raises DdpcaError(DDPCA_ENUMERIC) with the last good iterate in the .x attribute."""
-    keep = []
+    keep = {}  # id(object) -> its marshalled arrays: an object occurring twice hands over the same pointers
     arr = (_CsrArg * len(systems))()
-    for k, m in enumerate(systems):
-        m = m.tocsr()
-        ptr, col, val = (np.ascontiguousarray(m.indptr, np.int64), np.ascontiguousarray(m.indices, np.int32),
-                         np.ascontiguousarray(m.data, np.float64))
-        keep += [ptr, col, val]
-        arr[k] = _CsrArg(m.shape[0], m.shape[1], ptr.ctypes.data, col.ctypes.data, val.ctypes.data)
+    for k, obj in enumerate(systems):
+        if id(obj) not in keep:
+            m = obj.tocsr()
+            keep[id(obj)] = (m.shape, np.ascontiguousarray(m.indptr, np.int64), np.ascontiguousarray(m.indices, np.int32),
+                             np.ascontiguousarray(m.data, np.float64))
+        shape, ptr, col, val = keep[id(obj)]
+        arr[k] = _CsrArg(shape[0], shape[1], ptr.ctypes.data, col.ctypes.data, val.ctypes.data)
     b = np.ascontiguousarray(b, dtype=np.float64)
     x = np.zeros_like(b)
     its = np.zeros(len(systems), np.int64)

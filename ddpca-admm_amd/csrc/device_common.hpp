@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdlib>
 #include <mutex>
@@ -58,6 +59,27 @@ struct SyncCallGuard {
         if (!CaptureLock::capturing()) g = std::shared_lock<std::shared_mutex>(CaptureLock::mutex());
     }
 };
+
+// What `body` enqueues on `s`, as an executable graph: a thread-local capture under the capture
+// lock.  A throw out of `body` ends the capture and discards its graph before it goes on, so the
+// thread is never left inside a capture.
+template <typename Body>
+hipGraphExec_t capture_graph(hipStream_t s, Body&& body) {
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ge = nullptr;
+    CaptureSection capture_section;
+    DDPCA_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    try {
+        body();
+    } catch (...) {
+        if (hipStreamEndCapture(s, &g) == hipSuccess && g) (void)hipGraphDestroy(g);
+        throw;
+    }
+    DDPCA_HIP(hipStreamEndCapture(s, &g));
+    DDPCA_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    DDPCA_HIP(hipGraphDestroy(g));
+    return ge;
+}
 
 // Owning device allocation.
 template <typename T>
@@ -123,6 +145,14 @@ struct DevSpan {
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
+inline int nb256(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }  // blocks of 256 threads
+
+// the sum over a wavefront, in every lane (xor butterfly: one fixed order)
+__device__ __forceinline__ double wsum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 
 // Make `device` current and check it is a gfx950 part (no silent fallback anywhere).
 void select_device(int device);

@@ -33,12 +33,6 @@ constexpr int kVtwTile = 256;   // rows of w one workgroup of k_eig_vtw stages i
 constexpr int kUpdTile = 64;    // rows per workgroup of k_eig_update (4 waves split the columns)
 constexpr int kGemmCols = 8;    // output columns per workgroup of k_eig_gemm (S tile in LDS)
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // fixed-order sum of one value per thread of a 256-thread workgroup (valid in thread 0)
 __device__ __forceinline__ double block_sum(double v, double* red) {
     v = wsum(v);

@@ -31,12 +31,6 @@ struct DotArgs {
     int m;
 };
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // partial[k * gridDim.x + block] = sum over this block's grid-stride share of a_k . b_k
 __global__ __launch_bounds__(kBlock) void k_mdot(DotArgs d, int64_t n, double* partial) {
     double s[kMaxDots];

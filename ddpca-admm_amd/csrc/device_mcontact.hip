@@ -20,10 +20,10 @@
 // interface products (gamma, the aux right-hand side, the lambda right-hand side) of ALL owned
 // sides are each ONE SELL-64 operator whose columns index W, so each is one coalesced launch.
 // The surface mass solves (LDLT in the reference, < 120000 rows) run as ONE batched Jacobi-PCG
-// over every owned side (ELL-64 rows, per-side scalars) to a 1e-14 relative residual.
+// over every owned side (ELL-64 rows, per-side scalars) to a 1e-14 relative residual
+// (device_mass.hpp); the ranks' exchanges go through a Transport (device_transport.hpp).
 // Everything runs on the batch's single stream.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
@@ -31,22 +31,22 @@
 #include <chrono>
 #include <climits>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstring>
-#include <deque>
 #include <map>
 #include <memory>
-#include <mutex>
 #include <numeric>
 #include <thread>
 #include <tuple>
 #include <unordered_map>
 
 #include "../../include/ddpca_amd.h"
+#include "csr_ops.hpp"
 #include "device_eigs.hpp"
+#include "device_mass.hpp"
 #include "device_mgpis.hpp"
 #include "device_stress.hpp"
+#include "device_transport.hpp"
 #include "problem.hpp"
 #include "subdomain_ops.hpp"
 
@@ -54,38 +54,7 @@ using namespace ddpca;
 
 namespace {
 
-#define DDPCA_NCCL(call)                                                                                  \
-    do {                                                                                                  \
-        ncclResult_t r_ = (call);                                                                         \
-        if (r_ != ncclSuccess) throw ApiError(DDPCA_ECOMM, std::string(#call) + ": " + ncclGetErrorString(r_)); \
-    } while (0)
-
-Csr transpose(const Csr& A) {
-    Csr T;
-    T.nrow = A.ncol;
-    T.ncol = A.nrow;
-    T.ptr.assign(T.nrow + 1, 0);
-    for (int32_t c : A.col) T.ptr[c + 1]++;
-    for (int64_t r = 0; r < T.nrow; ++r) T.ptr[r + 1] += T.ptr[r];
-    T.col.resize(A.col.size());
-    T.val.resize(A.val.size());
-    std::vector<int64_t> fill(T.ptr.begin(), T.ptr.end() - 1);
-    for (int64_t r = 0; r < A.nrow; ++r)
-        for (int64_t k = A.ptr[r]; k < A.ptr[r + 1]; ++k) {
-            const int64_t p = fill[A.col[k]]++;
-            T.col[p] = (int32_t)r;
-            T.val[p] = A.val[k];
-        }
-    return T;
-}
-
 // ------------------------------------------------------------------------------- kernels
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ double csr_row(const int64_t* ptr, const int32_t* col, const double* val, const double* x,
                                           int64_t r) {
     double s = 0.0;
@@ -302,342 +271,6 @@ __global__ __launch_bounds__(256) void k_inpo_node(const int64_t* ptr, const int
     }
 }
 
-// ---- batched Jacobi-PCG over the owned sides' surface mass systems.  Rows of all systems
-// are concatenated, each padded to a multiple of 64 (ELL-64: chunk = 64 rows = one wave,
-// lane = row, slot k at (off[c]+k)*64 + lane); per-system scalars live in PcgScal.
-struct EllArgs {
-    const int32_t* slots;
-    const int64_t* off;
-    const int32_t* col;
-    const double* val;
-    const int32_t* csys;
-    const double* dinv;
-    int64_t nch;
-};
-
-// r = b, x = 0, z = D^-1 b, p = q = 0; partials (b.z, b.b) per chunk
-__global__ __launch_bounds__(256) void k_mcg_init(const double* b, const double* dinv, double* x, double* r, double* z,
-                                                  double* p, double* q, double* partial, int64_t nrow) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nrow) return;
-    const double bi = b[i], zi = dinv[i] * bi;
-    x[i] = 0.0;
-    r[i] = bi;
-    z[i] = zi;
-    p[i] = 0.0;
-    q[i] = 0.0;
-    const double a = wsum(bi * zi), c = wsum(bi * bi);
-    if ((threadIdx.x & 63) == 0) {
-        partial[2 * (i >> 6)] = a;
-        partial[2 * (i >> 6) + 1] = c;
-    }
-}
-
-// q = A z + beta q, p = z + beta p; partial p.q per chunk
-__global__ __launch_bounds__(256) void k_mcg_spmv(EllArgs e, const PcgScal* sc, const double* z, double* q, double* p,
-                                                  double* partial, int ostride = 2) {
-    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= e.nch) return;
-    const int sys = e.csys[c];
-    if (sc[sys].done) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t row = c * 64 + lane;
-    const int ns = e.slots[c];
-    const int32_t* cp = e.col + e.off[c] * 64 + lane;
-    const double* vp = e.val + e.off[c] * 64 + lane;
-    double s = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < ns; ++k) s += vp[(int64_t)k * 64] * z[cp[(int64_t)k * 64]];
-    const double be = sc[sys].beta;
-    const double qi = s + be * q[row], pi = z[row] + be * p[row];
-    q[row] = qi;
-    p[row] = pi;
-    const double d = wsum(pi * qi);
-    if (lane == 0) partial[ostride * c] = d;
-}
-
-// k_mcg_spmv over a batch whose second half repeats the first half's matrices R rows further on
-// (the fused w|v interface update: both sides' v systems carry the w systems' inteMass): a wave
-// takes chunk c and its twin c + nch2, reads the stored entries once and gathers z at j and j + R.
-// Each row's sum runs over the same slots in the same order as in k_mcg_spmv, so q, p and the
-// partials are bit for bit those of the unpaired launch; the matrix stream is halved.
-__global__ __launch_bounds__(256) void k_mcg_spmv2(EllArgs e, const PcgScal* sc, const double* z, double* q, double* p,
-                                                   double* partial, int ostride, int64_t R, int64_t nch2) {
-    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= nch2) return;
-    const int sw = e.csys[c], sv = e.csys[c + nch2];
-    const bool dw = sc[sw].done != 0, dv = sc[sv].done != 0;
-    if (dw && dv) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t row = c * 64 + lane;
-    const int ns = e.slots[c];
-    const int32_t* cp = e.col + e.off[c] * 64 + lane;
-    const double* vp = e.val + e.off[c] * 64 + lane;
-    const double* zv = z + R;
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < ns; ++k) {
-        const double v = vp[(int64_t)k * 64];
-        const int32_t j = cp[(int64_t)k * 64];
-        s0 += v * z[j];
-        s1 += v * zv[j];
-    }
-    if (!dw) {
-        const double be = sc[sw].beta;
-        const double qi = s0 + be * q[row], pi = z[row] + be * p[row];
-        q[row] = qi;
-        p[row] = pi;
-        const double d = wsum(pi * qi);
-        if (lane == 0) partial[ostride * c] = d;
-    }
-    if (!dv) {
-        const double be = sc[sv].beta;
-        const int64_t rv = row + R;
-        const double qi = s1 + be * q[rv], pi = z[rv] + be * p[rv];
-        q[rv] = qi;
-        p[rv] = pi;
-        const double d = wsum(pi * qi);
-        if (lane == 0) partial[ostride * (c + nch2)] = d;
-    }
-}
-
-// k_mcg_axpy with alpha computed in place of a k_mcg_fin(kMcgAlpha) launch: every wave sums its
-// system's p.q chunk partials (ppq, written by k_mcg_spmv with stride 1 -- not the (r.r, r.z)
-// pairs this kernel writes) in one fixed order, so all waves hold the same alpha; the system's
-// first chunk stores alpha / p.q and the breakdown flag as k_mcg_fin did.  On a breakdown (p.q
-// not positive or not finite) every wave sees the same p.q and leaves x, r, z untouched, so x
-// keeps the last good iterate as with the separate k_mcg_fin launch.  Every wave re-reads its
-// system's partials (chunks^2 L2 reads per system), so MassBatch takes this form only up to
-// kMcgFuseMaxChunks chunks (65,536 rows) per system; the headline's sides have up to ~300.
-constexpr int64_t kMcgFuseMaxChunks = 1024;
-__global__ __launch_bounds__(256) void k_mcg_axpy_fa(EllArgs e, PcgScal* sc, double* x, double* r, double* z,
-                                                     const double* p, const double* q, double* partial,
-                                                     const double* ppq, const int64_t* cb, PcgMirror* mirror) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t c = i >> 6;
-    if (c >= e.nch) return;
-    const int sys = e.csys[c];
-    if (sc[sys].done) return;
-    const int lane = threadIdx.x & 63;
-    double pq = 0.0;
-    for (int64_t k = cb[sys] + lane; k < cb[sys + 1]; k += 64) pq += ppq[k];
-    pq = wsum(pq);
-    const double al = sc[sys].delta / pq;
-    const bool bad = !(pq > 0.0) || !isfinite(pq);  // the same in every wave of the system
-    if (c == cb[sys] && lane == 0) {
-        sc[sys].pq = pq;
-        sc[sys].alpha = al;
-        if (bad) {
-            sc[sys].fail = 1;
-            sc[sys].done = 1;
-            mirror_store(mirror + sys, sc[sys].iter, 1, 1);
-        }
-    }
-    if (bad) return;
-    x[i] += al * p[i];
-    const double ri = r[i] - al * q[i], zi = e.dinv[i] * ri;
-    r[i] = ri;
-    z[i] = zi;
-    const double a = wsum(ri * ri), b = wsum(ri * zi);
-    if (lane == 0) {
-        partial[2 * c] = a;
-        partial[2 * c + 1] = b;
-    }
-}
-
-// x += alpha p, r -= alpha q, z = D^-1 r; partials (r.r, r.z) per chunk
-__global__ __launch_bounds__(256) void k_mcg_axpy(EllArgs e, const PcgScal* sc, double* x, double* r, double* z,
-                                                  const double* p, const double* q, double* partial) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t c = i >> 6;
-    if (c >= e.nch) return;
-    const int sys = e.csys[c];
-    if (sc[sys].done) return;
-    const double al = sc[sys].alpha;
-    x[i] += al * p[i];
-    const double ri = r[i] - al * q[i], zi = e.dinv[i] * ri;
-    r[i] = ri;
-    z[i] = zi;
-    const double a = wsum(ri * ri), b = wsum(ri * zi);
-    if ((threadIdx.x & 63) == 0) {
-        partial[2 * c] = a;
-        partial[2 * c + 1] = b;
-    }
-}
-
-// ---- Chebyshev iteration on D^-1 M (MassBatch::cheb_; Saad, Iterative Methods, Alg. 12.1): a fixed
-// number of steps from setup bounds of each system's spectrum, one launch per step, no reductions;
-// the CG below then restarts from its iterate (k_mcg_restart) and usually finds it converged.
-// x = 0, r = b, d = D^-1 b / theta_sys
-__global__ __launch_bounds__(256) void k_mcheb_init(const double* b, const double* dinv, const double* ith,
-                                                    const int32_t* csys, double* x, double* r, double* d, int64_t nrow) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nrow) return;
-    const double bi = b[i];
-    x[i] = 0.0;
-    r[i] = bi;
-    d[i] = ith[csys[i >> 6]] * dinv[i] * bi;
-}
-
-// step k: x += d, r -= M d, dn = c1 d + c2 D^-1 r (coef[(k nsys + sys) 2 + {0, 1}]); systems whose
-// step count kmax is reached keep their x, r.  The paired form (MassBatch::paired_) reads the
-// shared matrix once for chunk c and its twin c + nch2, as k_mcg_spmv2.
-template <bool PAIR>
-__global__ __launch_bounds__(256) void k_mcheb_step(EllArgs e, const double* coef, const int32_t* kmax, int nsys, int k,
-                                                    const double* d, double* dn, double* x, double* r, int64_t R,
-                                                    int64_t nch_launch) {
-    const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (c >= nch_launch) return;
-    const int sw = e.csys[c];
-    const int sv = PAIR ? e.csys[c + nch_launch] : sw;
-    const bool aw = k < kmax[sw], av = PAIR && k < kmax[sv];
-    if (!aw && !av) return;
-    const int lane = threadIdx.x & 63;
-    const int64_t row = c * 64 + lane;
-    const int ns = e.slots[c];
-    const int32_t* cp = e.col + e.off[c] * 64 + lane;
-    const double* vp = e.val + e.off[c] * 64 + lane;
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll 4
-    for (int q = 0; q < ns; ++q) {
-        const double v = vp[(int64_t)q * 64];
-        const int32_t j = cp[(int64_t)q * 64];
-        s0 += v * d[j];
-        if (PAIR) s1 += v * d[j + R];
-    }
-    auto upd = [&](int sys, int64_t i, double sum) {
-        const double di = d[i];
-        x[i] += di;
-        const double ri = r[i] - sum;
-        r[i] = ri;
-        const double* cc = coef + 2 * ((int64_t)k * nsys + sys);
-        dn[i] = cc[0] * di + cc[1] * e.dinv[i] * ri;
-    };
-    if (aw) upd(sw, row, s0);
-    if (av) upd(sv, row + R, s1);
-}
-
-// CG restart from the Chebyshev iterate: z = D^-1 r, p = q = 0; partials (r.z, r.r) per chunk and
-// b.b per chunk at bb (the stop rule stays relative to ||b||)
-__global__ __launch_bounds__(256) void k_mcg_restart(const double* b, const double* dinv, const double* r, double* z,
-                                                     double* p, double* q, double* partial, double* bbp, int64_t nrow) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nrow) return;
-    const double ri = r[i], zi = dinv[i] * ri, bi = b[i];
-    z[i] = zi;
-    p[i] = 0.0;
-    q[i] = 0.0;
-    const double a = wsum(ri * zi), c = wsum(ri * ri), d = wsum(bi * bi);
-    if ((threadIdx.x & 63) == 0) {
-        partial[2 * (i >> 6)] = a;
-        partial[2 * (i >> 6) + 1] = c;
-        bbp[i >> 6] = d;
-    }
-}
-
-enum McgWhat { kMcgInit = 0, kMcgAlpha = 1, kMcgBeta = 2 };
-
-// per-system scalars: one workgroup per system, fixed order over its chunks
-__global__ __launch_bounds__(256) void k_mcg_fin(int what, const double* partial, const int64_t* cb, PcgScal* scv,
-                                                 PcgMirror* mirror) {
-    const int sys = blockIdx.x;
-    PcgScal* sc = scv + sys;
-    if (what != kMcgInit && sc->done) return;
-    __shared__ double r0[4], r1[4];
-    // four independent accumulator pairs per thread (loads in flight together), fixed order
-    double av[4] = {0.0, 0.0, 0.0, 0.0}, bv[4] = {0.0, 0.0, 0.0, 0.0};
-    const int64_t k1 = cb[sys + 1];
-    for (int64_t k = cb[sys] + threadIdx.x; k < k1; k += 4 * 256) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int64_t q = k + 256 * u;
-            if (q < k1) {
-                av[u] += partial[2 * q];
-                bv[u] += partial[2 * q + 1];
-            }
-        }
-    }
-    double a = wsum((av[0] + av[1]) + (av[2] + av[3]));
-    double b = wsum((bv[0] + bv[1]) + (bv[2] + bv[3]));
-    if ((threadIdx.x & 63) == 0) {
-        r0[threadIdx.x >> 6] = a;
-        r1[threadIdx.x >> 6] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    a = (r0[0] + r0[1]) + (r0[2] + r0[3]);
-    b = (r1[0] + r1[1]) + (r1[2] + r1[3]);
-    if (what == kMcgInit) {
-        // x0 = 0: ||r0||^2 = b.b
-        sc->delta = a;
-        sc->bb = b;
-        sc->rr = b;
-        sc->tol2 = sc->tol2 * b;
-        sc->beta = 0.0;
-        sc->iter = 0;
-        sc->fail = 0;
-        sc->done = (b <= sc->tol2 || sc->maxit <= 0) ? 1 : 0;
-        mirror_store(mirror + sys, 0, sc->done, 0);
-    } else if (what == kMcgAlpha) {
-        sc->pq = a;
-        if (!(a > 0.0) || !isfinite(a)) {
-            sc->fail = 1;
-            sc->done = 1;
-            mirror_store(mirror + sys, sc->iter, 1, 1);
-        }
-        sc->alpha = sc->delta / a;
-    } else {
-        sc->rr = a;
-        sc->iter += 1;
-        if (!isfinite(a) || !isfinite(b)) sc->fail = 1;
-        if (sc->fail || a <= sc->tol2 || sc->iter >= sc->maxit) sc->done = 1;
-        sc->beta = b / sc->delta;
-        sc->delta = b;
-        mirror_store(mirror + sys, sc->iter, sc->done, sc->fail);
-    }
-}
-
-// the CG's scalars after k_mcg_restart: delta = r.z, rr = r.r, bb = b.b (one workgroup per system,
-// a fixed order), tol2 scaled by b.b as k_mcg_fin's init does
-__global__ __launch_bounds__(256) void k_mcg_fin_restart(const double* partial, const double* bbp, const int64_t* cb,
-                                                         PcgScal* scv, PcgMirror* mirror) {
-    const int sys = blockIdx.x;
-    PcgScal* sc = scv + sys;
-    __shared__ double r0[4], r1[4], r2[4];
-    double a = 0.0, b = 0.0, c = 0.0;
-    for (int64_t k = cb[sys] + threadIdx.x; k < cb[sys + 1]; k += 256) {
-        a += partial[2 * k];
-        b += partial[2 * k + 1];
-        c += bbp[k];
-    }
-    a = wsum(a);
-    b = wsum(b);
-    c = wsum(c);
-    if ((threadIdx.x & 63) == 0) {
-        r0[threadIdx.x >> 6] = a;
-        r1[threadIdx.x >> 6] = b;
-        r2[threadIdx.x >> 6] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    a = (r0[0] + r0[1]) + (r0[2] + r0[3]);
-    b = (r1[0] + r1[1]) + (r1[2] + r1[3]);
-    c = (r2[0] + r2[1]) + (r2[2] + r2[3]);
-    sc->delta = a;
-    sc->bb = c;
-    sc->rr = b;
-    sc->tol2 = sc->tol2 * c;
-    sc->beta = 0.0;
-    sc->iter = 0;
-    sc->fail = 0;
-    sc->done = (b <= sc->tol2 || sc->maxit <= 0 || !(c > 0.0)) ? 1 : 0;
-    if (!isfinite(a) || !isfinite(b)) {
-        sc->fail = 1;
-        sc->done = 1;
-    }
-    mirror_store(mirror + sys, 0, sc->done, sc->fail);
-}
-
 // All MONITOR pair norms of an iteration in two launches (instead of two per vector pair, 3.63 ->
 // 3.40 ms interface step at the headline, profiles/r03ab): block b of k_pair_norms_all is block
 // b - blk0[g] of segment g = bseg[b] (256 elements, the pair's squared difference and square), and
@@ -834,8 +467,6 @@ __global__ void k_fuse_aux_lambda(double* state, const double* wv, const double*
     state[R + i] = -v;
 }
 
-inline int nb256(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
-
 // Row lists -> SELL-64 (rows padded to a multiple of 64; padding slots: column 0, value 0).
 using Rows = std::vector<std::vector<std::pair<int64_t, double>>>;
 
@@ -892,516 +523,6 @@ bool two_streams() {
     const char* v = std::getenv("DDPCA_STREAMS");
     return !(v && v[0] == '1');
 }
-
-// scs[h][i] = sc[i] with done forced on the other half's systems / sc[i] = its half's copy
-__global__ void k_scal_split(const PcgScal* sc, PcgScal* scs, const int32_t* half, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int h = 0; h < 2; ++h) {
-        PcgScal v = sc[i];
-        if (half[i] != h) v.done = 1;
-        scs[h * n + i] = v;
-    }
-}
-__global__ void k_scal_merge(PcgScal* sc, const PcgScal* scs, const int32_t* half, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) sc[i] = scs[half[i] * n + i];
-}
-
-// Extreme eigenvalues of D^-1 M for an SPD CSR M (MassBatch's Chebyshev steps): Lanczos on the
-// symmetric D^-1/2 M D^-1/2 (m steps from a fixed start vector), Ritz extremes by bisection on
-// the tridiagonal (Sturm counts); *gersh = max_i sum_j |M_ij| / M_ii, an upper bound
-void mass_spectrum(const Csr& M, int m, double* lmin, double* lmax, double* gersh) {
-    const int64_t n = M.nrow;
-    std::vector<double> dis(n, 0.0);
-    double g = 0.0;
-    for (int64_t r = 0; r < n; ++r) {
-        double dg = 0.0, sa = 0.0;
-        for (int64_t k = M.ptr[r]; k < M.ptr[r + 1]; ++k) {
-            sa += std::abs(M.val[k]);
-            if (M.col[k] == r) dg = M.val[k];
-        }
-        dis[r] = dg > 0.0 ? 1.0 / std::sqrt(dg) : 0.0;
-        if (dg > 0.0) g = std::max(g, sa / dg);
-    }
-    *gersh = g;
-    m = (int)std::min<int64_t>(m, n);
-    std::vector<double> v(n), vp(n, 0.0), w(n), alpha, beta;
-    double nv = 0.0;
-    for (int64_t i = 0; i < n; ++i) v[i] = 1.0 + 0.5 * std::sin(0.7 * (double)i + 0.3), nv += v[i] * v[i];
-    nv = std::sqrt(nv);
-    for (double& x : v) x /= nv;
-    double bprev = 0.0;
-    for (int j = 0; j < m; ++j) {
-        for (int64_t r = 0; r < n; ++r) {
-            double acc = 0.0;
-            for (int64_t k = M.ptr[r]; k < M.ptr[r + 1]; ++k) acc += M.val[k] * dis[M.col[k]] * v[M.col[k]];
-            w[r] = dis[r] * acc - bprev * vp[r];
-        }
-        double a = 0.0;
-        for (int64_t r = 0; r < n; ++r) a += w[r] * v[r];
-        double b = 0.0;
-        for (int64_t r = 0; r < n; ++r) {
-            w[r] -= a * v[r];
-            b += w[r] * w[r];
-        }
-        b = std::sqrt(b);
-        alpha.push_back(a);
-        if (j + 1 == m || !(b > 1e-14)) break;
-        beta.push_back(b);
-        for (int64_t r = 0; r < n; ++r) {
-            vp[r] = v[r];
-            v[r] = w[r] / b;
-        }
-        bprev = b;
-    }
-    const int t = (int)alpha.size();
-    auto count_below = [&](double x) {  // eigenvalues of T below x (Sturm sequence)
-        int c = 0;
-        double q = alpha[0] - x;
-        if (q < 0) ++c;
-        for (int i = 1; i < t; ++i) {
-            const double qq = std::abs(q) < 1e-300 ? 1e-300 : q;
-            q = alpha[i] - x - beta[i - 1] * beta[i - 1] / qq;
-            if (q < 0) ++c;
-        }
-        return c;
-    };
-    double lo = 0.0, hi = 0.0;
-    for (int i = 0; i < t; ++i) {
-        const double rad = (i > 0 ? std::abs(beta[i - 1]) : 0.0) + (i + 1 < t ? std::abs(beta[i]) : 0.0);
-        lo = std::min(lo, alpha[i] - rad);
-        hi = std::max(hi, alpha[i] + rad);
-    }
-    auto kth = [&](int k) {  // the k-th smallest eigenvalue (0-based)
-        double a = lo, b = hi;
-        for (int it = 0; it < 200; ++it) {
-            const double mid = 0.5 * (a + b);
-            if (count_below(mid) > k) b = mid;
-            else a = mid;
-        }
-        return 0.5 * (a + b);
-    };
-    *lmin = kth(0);
-    *lmax = kth(t - 1);
-}
-
-// Batched surface-mass solver: one graph of `k` CG iterations over every system, replayed
-// until every system reports done through the host-mapped mirror.  Chebyshev mode (cheb_, the
-// default where every system's steps fit kChebMax): a fixed-length Chebyshev iteration first, one
-// launch per step, then the CG from its iterate -- usually converged at its first check.
-constexpr int64_t kChebMax = 120;
-class MassBatch {
-public:
-    int nsys = 0;
-    int64_t nrow = 0, nch = 0;
-    DevBuf<int32_t> slots, col, csys;
-    DevBuf<int64_t> off, cb;
-    DevBuf<double> val, dinv, b, x, r, z, p, q, partial;
-    DevBuf<PcgScal> sc;
-    PcgScal* sc_host = nullptr;
-    MirrorBuf mirror;
-    int64_t k = 8;
-    int64_t last_iters = 0;
-    double alg_bytes = 0.0;  // accumulated by check(): init + iterations of every system
-    // Chebyshev mode: spectral bounds per system from build(), steps from the first solve's rtol
-    bool cheb_ = false;
-    int64_t cheb_k_ = 0;                       // steps of the captured Chebyshev graph (max over systems)
-    std::vector<double> lam_lo_, lam_hi_;      // D^-1 M spectrum bounds used, per system
-    std::vector<int32_t> cheb_ks_;             // steps per system
-
-    // A[i] = system i (rows m_i), placed at rows roff[i] (multiples of 64) of nrow_total.
-    void build(const std::vector<const Csr*>& A, const std::vector<int64_t>& roff, int64_t nrow_total) {
-        nsys = (int)A.size();
-        nrow = nrow_total;
-        nch = nrow / 64;
-        std::vector<int32_t> sl(std::max<int64_t>(nch, 1), 0), cs(std::max<int64_t>(nch, 1), 0);
-        std::vector<int64_t> of(nch + 1, 0), c0(nsys + 1, nch);
-        std::vector<double> di(std::max<int64_t>(nrow, 1), 0.0);
-        for (int s = 0; s < nsys; ++s) {
-            const Csr& M = *A[s];
-            c0[s] = roff[s] / 64;
-            for (int64_t c = roff[s] / 64; c < (roff[s] + pad64(M.nrow)) / 64; ++c) {
-                cs[c] = s;
-                int64_t mx = 0;
-                for (int64_t r = (c * 64 - roff[s]); r < std::min(M.nrow, c * 64 - roff[s] + 64); ++r)
-                    mx = std::max(mx, M.ptr[r + 1] - M.ptr[r]);
-                sl[c] = (int32_t)mx;
-            }
-        }
-        for (int64_t c = 0; c < nch; ++c) of[c + 1] = of[c] + sl[c];
-        std::vector<int32_t> co(std::max<int64_t>(of[nch] * 64, 1), 0);
-        std::vector<double> va(std::max<int64_t>(of[nch] * 64, 1), 0.0);
-        for (int64_t c = 0; c < nch; ++c)
-            for (int64_t q2 = of[c]; q2 < of[c + 1]; ++q2)
-                for (int lane = 0; lane < 64; ++lane) co[q2 * 64 + lane] = (int32_t)(c * 64 + lane);  // pad: self, 0
-        for (int s = 0; s < nsys; ++s) {
-            const Csr& M = *A[s];
-            for (int64_t r0 = 0; r0 < M.nrow; ++r0) {
-                const int64_t g = roff[s] + r0, c = g / 64, lane = g % 64;
-                for (int64_t k2 = M.ptr[r0]; k2 < M.ptr[r0 + 1]; ++k2) {
-                    const int64_t q2 = of[c] + (k2 - M.ptr[r0]);
-                    co[q2 * 64 + lane] = (int32_t)(roff[s] + M.col[k2]);
-                    va[q2 * 64 + lane] = M.val[k2];
-                    if (M.col[k2] == r0) di[g] = 1.0 / M.val[k2];
-                }
-            }
-        }
-        // paired batch: systems i and i + nsys/2 share one matrix, R = nrow/2 rows apart
-        paired_ = nsys >= 2 && nsys % 2 == 0 && nrow % 128 == 0;
-        for (int s = 0; paired_ && s < nsys / 2; ++s)
-            paired_ = A[s] == A[s + nsys / 2] && roff[s + nsys / 2] == roff[s] + nrow / 2;
-        slots.upload(sl);
-        csys.upload(cs);
-        off.upload(of);
-        col.upload(co);
-        val.upload(va);
-        dinv.upload(di);
-        cb.upload(c0);
-        cb_host_ = c0;
-        // algorithmic bytes per system: init (b, D^-1 read; x r z p q written: 56 B per row) and
-        // per CG iteration -- k_mcg_spmv: stored entries (12 B), z gathered once, z, q, p read
-        // and q, p written; k_mcg_axpy: x, r read + written, z written, p, q, D^-1 read (112 B per row)
-        init_bytes_.assign(nsys, 0.0);
-        it_bytes_.assign(nsys, 0.0);
-        mat_bytes_.assign(nsys, 0.0);
-        for (int s = 0; s < nsys; ++s) {
-            const double rows = (double)A[s]->nrow, ent = (double)A[s]->nnz();
-            init_bytes_[s] = 56.0 * rows;
-            // (+ the p.q and (r.r, r.z) chunk partials written once and read once: 24 B each way per chunk)
-            it_bytes_[s] = 8.0 * rows + 40.0 * rows + 64.0 * rows + 48.0 * (double)(pad64(A[s]->nrow) / 64);
-            mat_bytes_[s] = 12.0 * ent;  // (k_mcg_spmv2: once per pair, for the pair's longer solve)
-        }
-        for (auto* v : {&b, &x, &r, &z, &p, &q}) {
-            v->alloc(std::max<int64_t>(nrow, 2));
-            v->zero();
-        }
-        partial.alloc(3 * std::max<int64_t>(nch, 1));  // (a, b) pairs + the fused form's p.q
-        sc.alloc(std::max(nsys, 1));
-        // Chebyshev bounds: [0.9 Ritz min, min(Gershgorin, 1.05 Ritz max)] of D^-1 M after 60 Lanczos
-        // steps (the CG that follows the fixed step count repairs an estimate that was off);
-        // DDPCA_MASS_CHEB=0 keeps the plain CG
-        const char* ce = std::getenv("DDPCA_MASS_CHEB");
-        cheb_ = !(ce && ce[0] == '0') && nsys > 0;
-        lam_lo_.assign(nsys, 0.0);
-        lam_hi_.assign(nsys, 0.0);
-        if (cheb_) {
-            std::vector<double> lo(nsys), hi(nsys), gh(nsys);
-#pragma omp parallel for schedule(dynamic, 1)
-            for (int s2 = 0; s2 < nsys; ++s2) mass_spectrum(*A[s2], 60, &lo[s2], &hi[s2], &gh[s2]);
-            for (int s2 = 0; s2 < nsys; ++s2) {
-                lam_lo_[s2] = 0.9 * lo[s2];
-                lam_hi_[s2] = std::min(gh[s2], 1.05 * hi[s2]);
-                if (!(lam_lo_[s2] > 0.0) || !(lam_hi_[s2] > lam_lo_[s2])) cheb_ = false;
-            }
-        }
-        // the ADMM loop's tolerance planned here, at setup: solve() uploads nothing while other
-        // in-process ranks may be capturing graphs
-        if (cheb_) cheb_plan(1.0e-14);
-        DDPCA_HIP(hipHostMalloc(reinterpret_cast<void**>(&sc_host), std::max(nsys, 1) * sizeof(PcgScal)));
-        mirror.alloc(nsys);
-    }
-    ~MassBatch() {
-        if (s2_) (void)hipStreamSynchronize(s2_);
-        drop_graphs();
-        if (ev_fork_) (void)hipEventDestroy(ev_fork_);
-        if (ev_join_) (void)hipEventDestroy(ev_join_);
-        if (s2_) (void)hipStreamDestroy(s2_);
-        if (sc_host) (void)hipHostFree(sc_host);
-    }
-
-    // x_out (nrow) = A^-1 b.  Asynchronous on `s` except for the host pacing of replays.
-    void solve(hipStream_t s, double* x_out, double rtol, int64_t maxit) {
-        if (nsys == 0) return;
-        solved_ = true;
-        if (x_out != x_target_) {
-            drop_graphs();
-            x_target_ = x_out;
-        }
-        if (cheb_ && rtol != cheb_rtol_) {
-            // a tolerance other than the setup plan's (1e-14, the ADMM loop's): re-plan and
-            // re-capture here -- the capture holds the library's capture lock (device_common.hpp)
-            drop_graphs();
-            cheb_plan(rtol);
-        }
-        if (!graph_) capture(s);
-        mirror.reset();  // the previous solve on `s` was paced to completion before this point
-        for (int i = 0; i < nsys; ++i) {
-            sc_host[i] = PcgScal{};
-            sc_host[i].tol2 = rtol * rtol;
-            sc_host[i].maxit = maxit;
-        }
-        DDPCA_HIP(hipMemcpyAsync(sc.p, sc_host, nsys * sizeof(PcgScal), hipMemcpyHostToDevice, s));
-        // Chebyshev mode: the fixed-length Chebyshev graph, then the CG restarted from its iterate
-        // (the host launches CG replays only once the mirror says a system is not done, or the
-        // stream drained); else x0 = 0 (warm starts from the previous ADMM iteration's solution:
-        // 39.3 -> 37.1 mass-CG iterations at the headline, no measurable gain, profiles/r03v)
-        int64_t launched0 = 0;
-        cheb_used_ = cheb_ && cgraph_;
-        if (cheb_used_) {
-            DDPCA_HIP(hipGraphLaunch(cgraph_, s));
-            launched0 = k + 1;
-        } else {
-            hipLaunchKernelGGL(k_mcg_init, dim3(nb256(nrow)), dim3(256), 0, s, b.p, dinv.p, x_out, r.p, z.p, p.p, q.p,
-                               partial.p, nrow);
-            hipLaunchKernelGGL(k_mcg_fin, dim3(nsys), dim3(256), 0, s, (int)kMcgInit, partial.p, cb.p, sc.p, mirror.dev);
-        }
-        if (split_) {
-            // fork into the two halves' streams, pace both, join and merge the scalars back
-            hipLaunchKernelGGL(k_scal_split, dim3(ceil_div(nsys, 64)), dim3(64), 0, s, sc.p, sc_half_.p, half_.p, nsys);
-            DDPCA_HIP(hipEventRecord(ev_fork_, s));
-            DDPCA_HIP(hipStreamWaitEvent(s2_, ev_fork_, 0));
-            hipStream_t st[2] = {s, s2_};
-            const int64_t hz[2] = {horizon(0), horizon(1)};
-            pace_halves(st, graph_h_, mirror, half_host_, k, launched0, graph1_h_, hz);
-            DDPCA_HIP(hipEventRecord(ev_join_, s2_));
-            DDPCA_HIP(hipStreamWaitEvent(s, ev_join_, 0));
-            hipLaunchKernelGGL(k_scal_merge, dim3(ceil_div(nsys, 64)), dim3(64), 0, s, sc.p, sc_half_.p, half_.p, nsys);
-            return;
-        }
-        pace_until_done(s, graph_, mirror, k, launched0, graph1_, horizon(-1));
-    }
-
-    // capture the solve's graphs now (create time, one thread) for solves into x_out: the first
-    // solve of an in-process rank then captures nothing while the other rank threads run
-    void prepare(hipStream_t s, double* x_out) {
-        if (nsys == 0) return;
-        if (x_out != x_target_) {
-            drop_graphs();
-            x_target_ = x_out;
-        }
-        if (!graph_) capture(s);
-    }
-
-    // Two-stream split of the systems (as MgpisDevice::set_split): two halves of equal rows, each
-    // half's CG iterations a graph of its own on its own stream, on a copy of the scalars where
-    // the other half's systems are done -- the latency-bound launches of the two halves overlap.
-    void set_split(bool on) {
-        on = on && nsys >= 2;
-        if (on && !s2_) {
-            DDPCA_HIP(hipStreamCreateWithFlags(&s2_, hipStreamNonBlocking));
-            DDPCA_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-            DDPCA_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-            sc_half_.alloc(2 * nsys);
-            // a paired batch splits by pairs, so that a pair's shared matrix is read by one half
-            const int nu = paired_ ? nsys / 2 : nsys;
-            std::vector<int64_t> rows(nu, 0);
-            std::vector<int> ord(nu);
-            for (int i = 0; i < nsys; ++i) rows[i % nu] += cb_host_[i + 1] - cb_host_[i];
-            for (int i = 0; i < nu; ++i) ord[i] = i;
-            std::stable_sort(ord.begin(), ord.end(), [&](int a, int c) { return rows[a] > rows[c]; });
-            half_host_.assign(nsys, 0);
-            int64_t w[2] = {0, 0};
-            for (int i : ord) {
-                const int h = w[1] < w[0] ? 1 : 0;
-                for (int j = i; j < nsys; j += nu) half_host_[j] = h;
-                w[h] += rows[i];
-            }
-            half_.upload(half_host_);
-        }
-        if (on != split_) drop_graphs();
-        split_ = on;
-    }
-
-    // alpha inside k_mcg_axpy_fa: default while every system has at most kMcgFuseMaxChunks chunks
-    // (each wave re-reads its system's p.q partials); DDPCA_MCG_FUSE_ALPHA=0 forces the separate
-    // k_mcg_fin launch, =1 the fused form at any size (read at graph capture)
-    int fuse_override = -1;  // ddpca_mass_solve: 0 / 1 forces the form (tests), -1 the rule below
-    bool fuse_alpha() const {
-        if (fuse_override >= 0) return fuse_override != 0;
-        const char* ef = std::getenv("DDPCA_MCG_FUSE_ALPHA");
-        if (ef && std::atoi(ef) == 0) return false;
-        if (ef && std::atoi(ef) == 1) return true;
-        for (int s = 0; s < nsys; ++s)
-            if (cb_host_[s + 1] - cb_host_[s] > kMcgFuseMaxChunks) return false;
-        return true;
-    }
-
-    // after the stream synchronised: iterations of the last solve, breakdown check
-    void check() {
-        last_iters = 0;
-        expect_.resize(nsys);
-        for (int i = 0; i < nsys; ++i) {
-            if (mirror.host[i].fail) {
-                solved_ = false;
-                throw ApiError(DDPCA_ENUMERIC, "surface mass CG breakdown in system " + std::to_string(i));
-            }
-            expect_[i] = mirror.host[i].iter;  // paces the next solve's tail
-            const int64_t ck = cheb_used_ ? (int64_t)cheb_ks_[i] : 0;
-            last_iters = std::max<int64_t>(last_iters, mirror.host[i].iter + ck);
-            if (solved_) {
-                int64_t mit = mirror.host[i].iter;
-                if (pair_used_) mit = i < nsys / 2 ? std::max(mit, mirror.host[i + nsys / 2].iter) : 0;
-                alg_bytes += init_bytes_[i] + (double)mirror.host[i].iter * it_bytes_[i] + (double)mit * mat_bytes_[i];
-                // Chebyshev: init (b, D^-1 read; x, r, d written) + per step (d gathered once, read;
-                // x, r read + written; D^-1 read; d' written: 56 B per row) + the matrix once per
-                // pair + the restart (b, r, D^-1 read; z, p, q written)
-                if (cheb_used_)
-                    alg_bytes += init_bytes_[i] * (40.0 / 56.0) + (double)ck * (it_bytes_[i] * (56.0 / 112.0)) +
-                                 (pair_used_ ? (i < nsys / 2 ? (double)ck * mat_bytes_[i] : 0.0) : (double)ck * mat_bytes_[i]) +
-                                 init_bytes_[i] * (48.0 / 56.0);
-            }
-        }
-        solved_ = false;
-    }
-
-private:
-    hipGraphExec_t graph_ = nullptr;
-    hipGraphExec_t graph_h_[2] = {nullptr, nullptr};
-    // one-iteration graphs for the tail (MgpisDevice::graph1_): past the systems' previous
-    // iteration counts the host queues single iterations two ahead of the slowest system
-    hipGraphExec_t graph1_ = nullptr;
-    hipGraphExec_t graph1_h_[2] = {nullptr, nullptr};
-    std::vector<int64_t> expect_;
-    int64_t horizon(int half) const {
-        const char* e = std::getenv("DDPCA_TAIL_PACING");
-        if ((e && std::atoi(e) == 0) || (int)expect_.size() != nsys) return INT64_MAX;
-        int64_t h = 0;
-        for (int i = 0; i < nsys; ++i) {
-            if (half >= 0 && half_host_[i] != half) continue;
-            if (expect_[i] <= 0) return INT64_MAX;
-            h = std::max(h, expect_[i]);
-        }
-        return h;
-    }
-    void drop_graphs() {
-        for (hipGraphExec_t* g : {&graph_h_[0], &graph_h_[1], &graph1_h_[0], &graph1_h_[1], &graph1_, &cgraph_}) {
-            if (*g) (void)hipGraphExecDestroy(*g);
-            *g = nullptr;
-        }
-        if (graph_ && !split_) (void)hipGraphExecDestroy(graph_);  // (split: graph_ aliases graph_h_[0])
-        graph_ = nullptr;
-    }
-    double* x_target_ = nullptr;
-    hipGraphExec_t cgraph_ = nullptr;  // Chebyshev: init, steps, CG restart
-    double cheb_rtol_ = -1.0;
-    bool cheb_used_ = false;
-    DevBuf<double> ccoef_, cith_;
-    DevBuf<int32_t> ckmax_;
-    // the step counts and coefficients for a relative residual rtol: per system kappa = hi / lo,
-    // K = ceil(ln(4 sqrt(kappa) / rtol) / ln sigma), sigma = (sqrt(kappa) + 1) / (sqrt(kappa) - 1)
-    // (the residual bound 2 sqrt(kappa) sigma^-K at half of rtol); none past kChebMax
-    void cheb_plan(double rtol) {
-        cheb_rtol_ = rtol;
-        cheb_ks_.assign(nsys, 0);
-        int64_t K = 0;
-        for (int s2 = 0; s2 < nsys; ++s2) {
-            const double kap = lam_hi_[s2] / lam_lo_[s2], sk = std::sqrt(kap);
-            const double sig = (sk + 1.0) / (sk - 1.0);
-            const int64_t ks = (int64_t)std::ceil(std::log(4.0 * sk / rtol) / std::log(sig));
-            cheb_ks_[s2] = (int32_t)std::max<int64_t>(1, ks);
-            K = std::max<int64_t>(K, cheb_ks_[s2]);
-        }
-        cheb_k_ = K;
-        // past kChebMax steps this tolerance runs the plain CG (capture() skips the Chebyshev
-        // graph); cheb_ stays set, so a later solve at a looser tolerance plans it again
-        if (K > kChebMax) return;
-        std::vector<double> coef((size_t)2 * K * nsys, 0.0), ith(nsys);
-        for (int s2 = 0; s2 < nsys; ++s2) {
-            const double th = 0.5 * (lam_hi_[s2] + lam_lo_[s2]), de = 0.5 * (lam_hi_[s2] - lam_lo_[s2]);
-            const double s1 = th / de;
-            ith[s2] = 1.0 / th;
-            double rho = 1.0 / s1;
-            for (int64_t kk = 0; kk < K; ++kk) {
-                const double rn = 1.0 / (2.0 * s1 - rho);
-                coef[2 * (kk * nsys + s2)] = rn * rho;
-                coef[2 * (kk * nsys + s2) + 1] = 2.0 * rn / de;
-                rho = rn;
-            }
-        }
-        ccoef_.upload(coef);
-        cith_.upload(ith);
-        ckmax_.upload(cheb_ks_);
-    }
-    bool split_ = false;
-    hipStream_t s2_ = nullptr;
-    hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
-    DevBuf<PcgScal> sc_half_;
-    DevBuf<int32_t> half_;
-    std::vector<int> half_host_;
-    std::vector<int64_t> cb_host_;
-    std::vector<double> init_bytes_, it_bytes_, mat_bytes_;
-    bool solved_ = false;
-    bool paired_ = false, pair_used_ = false;
-    void capture(hipStream_t s) {
-        if (cheb_ && cheb_k_ > 0 && cheb_k_ <= kChebMax) capture_cheb(s);
-        if (split_) {
-            capture_one(s, sc_half_.p, &graph_h_[0], k);
-            capture_one(s, sc_half_.p + nsys, &graph_h_[1], k);
-            if (k > 1) {
-                capture_one(s, sc_half_.p, &graph1_h_[0], 1);
-                capture_one(s, sc_half_.p + nsys, &graph1_h_[1], 1);
-            }
-            graph_ = graph_h_[0];  // marks the capture done (destroyed through graph_h_)
-            return;
-        }
-        capture_one(s, sc.p, &graph_, k);
-        if (k > 1) capture_one(s, sc.p, &graph1_, 1);
-    }
-    void capture_cheb(hipStream_t s) {
-        EllArgs e{slots.p, off.p, col.p, val.p, csys.p, dinv.p, nch};
-        const char* ep = std::getenv("DDPCA_MCG_PAIR");
-        const bool pair = paired_ && !(ep && std::atoi(ep) == 0);
-        hipGraph_t g;
-        CaptureSection capture_section;  // device_common.hpp CaptureLock
-        DDPCA_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        hipLaunchKernelGGL(k_mcheb_init, dim3(nb256(nrow)), dim3(256), 0, s, b.p, dinv.p, cith_.p, csys.p, x_target_, r.p,
-                           z.p, nrow);
-        double* d[2] = {z.p, p.p};
-        for (int64_t kk = 0; kk < cheb_k_; ++kk) {
-            const double* din = d[kk & 1];
-            double* dout = d[(kk + 1) & 1];
-            if (pair)
-                hipLaunchKernelGGL(k_mcheb_step<true>, dim3(ceil_div(nch / 2, 4)), dim3(256), 0, s, e, ccoef_.p, ckmax_.p,
-                                   nsys, (int)kk, din, dout, x_target_, r.p, nrow / 2, nch / 2);
-            else
-                hipLaunchKernelGGL(k_mcheb_step<false>, dim3(ceil_div(nch, 4)), dim3(256), 0, s, e, ccoef_.p, ckmax_.p,
-                                   nsys, (int)kk, din, dout, x_target_, r.p, (int64_t)0, nch);
-        }
-        hipLaunchKernelGGL(k_mcg_restart, dim3(nb256(nrow)), dim3(256), 0, s, b.p, dinv.p, r.p, z.p, p.p, q.p, partial.p,
-                           partial.p + 2 * nch, nrow);
-        hipLaunchKernelGGL(k_mcg_fin_restart, dim3(nsys), dim3(256), 0, s, partial.p, partial.p + 2 * nch, cb.p, sc.p,
-                           mirror.dev);
-        DDPCA_HIP(hipStreamEndCapture(s, &g));
-        DDPCA_HIP(hipGraphInstantiate(&cgraph_, g, nullptr, nullptr, 0));
-        DDPCA_HIP(hipGraphDestroy(g));
-    }
-    void capture_one(hipStream_t s, PcgScal* scp, hipGraphExec_t* out, int64_t iters) {
-        EllArgs e{slots.p, off.p, col.p, val.p, csys.p, dinv.p, nch};
-        hipGraph_t g;
-        CaptureSection capture_section;  // device_common.hpp CaptureLock
-        DDPCA_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const bool fa = fuse_alpha();
-        // DDPCA_MCG_PAIR=0: the unpaired k_mcg_spmv on a paired batch (bit-identical, A/B and tests)
-        const char* ep = std::getenv("DDPCA_MCG_PAIR");
-        const bool pair = paired_ && !(ep && std::atoi(ep) == 0);
-        pair_used_ = pair;
-        double* ppq = partial.p + 2 * nch;  // p.q per chunk
-        auto spmv = [&](double* part, int stride) {
-            if (pair)
-                hipLaunchKernelGGL(k_mcg_spmv2, dim3(ceil_div(nch / 2, 4)), dim3(256), 0, s, e, scp, z.p, q.p, p.p, part,
-                                   stride, nrow / 2, nch / 2);
-            else
-                hipLaunchKernelGGL(k_mcg_spmv, dim3(ceil_div(nch, 4)), dim3(256), 0, s, e, scp, z.p, q.p, p.p, part, stride);
-        };
-        for (int64_t it = 0; it < iters; ++it) {
-            if (fa) {
-                spmv(ppq, 1);
-                hipLaunchKernelGGL(k_mcg_axpy_fa, dim3(nb256(nrow)), dim3(256), 0, s, e, scp, x_target_, r.p, z.p, p.p,
-                                   q.p, partial.p, (const double*)ppq, cb.p, mirror.dev);
-            } else {
-                spmv(partial.p, 2);
-                hipLaunchKernelGGL(k_mcg_fin, dim3(nsys), dim3(256), 0, s, (int)kMcgAlpha, partial.p, cb.p, scp, mirror.dev);
-                hipLaunchKernelGGL(k_mcg_axpy, dim3(nb256(nrow)), dim3(256), 0, s, e, scp, x_target_, r.p, z.p, p.p, q.p,
-                                   partial.p);
-            }
-            hipLaunchKernelGGL(k_mcg_fin, dim3(nsys), dim3(256), 0, s, (int)kMcgBeta, partial.p, cb.p, scp, mirror.dev);
-        }
-        DDPCA_HIP(hipStreamEndCapture(s, &g));
-        DDPCA_HIP(hipGraphInstantiate(out, g, nullptr, nullptr, 0));
-        DDPCA_HIP(hipGraphDestroy(g));
-    }
-};
 
 }  // namespace
 
@@ -1479,151 +600,6 @@ struct CoarseDev {
     ~CoarseDev() {
         if (ev_in) (void)hipEventDestroy(ev_in);
         if (ev_out) (void)hipEventDestroy(ev_out);
-    }
-};
-
-// ============================================================================= transport
-// The exchanges of a multi-rank run, all stream-ordered on the rank's stream:
-//   exchange()      the gamma halves of cross-rank interfaces (one grouped send/recv per peer)
-//   allreduce_sum() the MONITOR norms and the coarse right-hand side every iteration, the dense
-//                   coarse matrix once at setup
-// RcclTransport is the production path (RCCL over xGMI); LocalTransport connects the handles of
-// ONE process through host-staged copies (mcontact_gpu_comm_local) so the multi-rank bookkeeping
-// (owner maps, gamma offsets, rank-local coarse rows) runs on a single GPU in the tests.
-struct Transport {
-    struct Msg {
-        int peer;
-        int64_t tag;  // interface index
-        const double* send;
-        double* recv;
-        int64_t n;
-    };
-    virtual ~Transport() = default;
-    virtual void allreduce_sum(double* buf, int64_t n, hipStream_t st) = 0;
-    virtual void exchange(const std::vector<Msg>& msgs, hipStream_t st) = 0;
-};
-
-struct RcclTransport : Transport {
-    ncclComm_t comm = nullptr;
-    ~RcclTransport() override {
-        if (comm) (void)ncclCommDestroy(comm);
-    }
-    void allreduce_sum(double* buf, int64_t n, hipStream_t st) override {
-        DDPCA_NCCL(ncclAllReduce(buf, buf, (size_t)n, ncclDouble, ncclSum, comm, st));
-    }
-    void exchange(const std::vector<Msg>& msgs, hipStream_t st) override {
-        DDPCA_NCCL(ncclGroupStart());
-        for (const Msg& m : msgs) {
-            DDPCA_NCCL(ncclSend(m.send, (size_t)m.n, ncclDouble, m.peer, comm, st));
-            DDPCA_NCCL(ncclRecv(m.recv, (size_t)m.n, ncclDouble, m.peer, comm, st));
-        }
-        DDPCA_NCCL(ncclGroupEnd());
-    }
-};
-
-// Timing-only transport (mcontact_gpu_comm_loopback): every receive from peer p gets what this
-// rank sent p, as an on-device copy on the solve stream; all-reduces keep this rank's own values.
-// One rank of an N-rank layout then runs its own share of the work on a single GPU.
-struct LoopbackTransport : Transport {
-    void allreduce_sum(double*, int64_t, hipStream_t) override {}
-    void exchange(const std::vector<Msg>& msgs, hipStream_t st) override {
-        for (const Msg& m : msgs)
-            if (m.n) DDPCA_HIP(hipMemcpyAsync(m.recv, m.send, (size_t)m.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-};
-
-// Rendezvous of the ranks of one process (each rank's calls come from its own host thread).
-struct LocalHub {
-    int n = 0;
-    std::mutex mu;
-    std::condition_variable cv;
-    int arrived = 0;
-    int64_t generation = 0;
-    bool broken = false;
-    std::vector<std::vector<double>> slot;  // allreduce staging per rank
-    // posted sends per (src, dst) in issue order -- matched against the receiver's receives from
-    // src in ITS issue order, as RCCL matches grouped ncclSend / ncclRecv pairs per peer (tags and
-    // sizes are only checked, never used for matching: an ordering bug fails here as on the wire)
-    struct Posted {
-        int64_t tag;
-        const double* buf;
-        int64_t n;
-    };
-    std::map<std::pair<int, int>, std::deque<Posted>> post;
-    void barrier() {
-        std::unique_lock<std::mutex> lk(mu);
-        if (broken) throw ApiError(DDPCA_ECOMM, "local transport: a peer failed");
-        const int64_t g = generation;
-        if (++arrived == n) {
-            arrived = 0;
-            ++generation;
-            cv.notify_all();
-        } else if (!cv.wait_for(lk, std::chrono::seconds(120), [&] { return generation != g || broken; }) || broken) {
-            broken = true;
-            cv.notify_all();
-            throw ApiError(DDPCA_ECOMM, "local transport: peers did not arrive");
-        }
-    }
-};
-
-struct LocalTransport : Transport {
-    std::shared_ptr<LocalHub> hub;
-    int rank = 0;
-    void allreduce_sum(double* buf, int64_t n, hipStream_t st) override {
-        auto& mine = hub->slot[rank];
-        mine.resize(n);
-        DDPCA_HIP(hipMemcpyAsync(mine.data(), buf, n * sizeof(double), hipMemcpyDeviceToHost, st));
-        DDPCA_HIP(hipStreamSynchronize(st));
-        hub->barrier();
-        std::vector<double> sum(n, 0.0);
-        for (int q = 0; q < hub->n; ++q)  // rank order: every rank gets the same bits
-            for (int64_t i = 0; i < n; ++i) sum[i] += hub->slot[q][i];
-        DDPCA_HIP(hipMemcpyAsync(buf, sum.data(), n * sizeof(double), hipMemcpyHostToDevice, st));
-        DDPCA_HIP(hipStreamSynchronize(st));
-        hub->barrier();  // nobody restages before every rank has read the slots
-    }
-    void exchange(const std::vector<Msg>& msgs, hipStream_t st) override {
-        DDPCA_HIP(hipStreamSynchronize(st));
-        {
-            std::lock_guard<std::mutex> lk(hub->mu);
-            for (const Msg& m : msgs) hub->post[{rank, m.peer}].push_back({m.tag, m.send, m.n});
-        }
-        hub->barrier();
-        std::string err;
-        for (const Msg& m : msgs) {
-            LocalHub::Posted p{};
-            {
-                std::lock_guard<std::mutex> lk(hub->mu);
-                auto& q = hub->post[{m.peer, rank}];
-                if (q.empty()) {
-                    err = "local transport: receive from rank " + std::to_string(m.peer) + " has no matching send";
-                    break;
-                }
-                p = q.front();
-                q.pop_front();
-            }
-            if (p.tag != m.tag || p.n != m.n) {
-                err = "local transport: message order differs between ranks " + std::to_string(m.peer) + " and " +
-                      std::to_string(rank) + " (tag " + std::to_string(p.tag) + " sent, " + std::to_string(m.tag) +
-                      " expected)";
-                break;
-            }
-            DDPCA_HIP(hipMemcpyAsync(m.recv, p.buf, m.n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        }
-        DDPCA_HIP(hipStreamSynchronize(st));
-        if (!err.empty()) {
-            std::lock_guard<std::mutex> lk(hub->mu);
-            hub->broken = true;
-            hub->cv.notify_all();
-            throw ApiError(DDPCA_ECOMM, err);
-        }
-        hub->barrier();  // the peers' send buffers stay untouched until every copy has landed
-        std::lock_guard<std::mutex> lk(hub->mu);
-        for (const Msg& m : msgs)
-            if (!hub->post[{rank, m.peer}].empty()) {
-                hub->broken = true;
-                throw ApiError(DDPCA_ECOMM, "local transport: a send to rank " + std::to_string(m.peer) + " was not received");
-            }
     }
 };
 
@@ -1986,7 +962,7 @@ void build(ddpca_mcontact& H, Problem& P) {
             }
             if (fuse) continue;
             // aux RHS: systTran_pena^T u + inteMass lambda + inteInpo gamma
-            const Csr tTp = transpose(itf.systTran_pena[s]);
+            const Csr tTp = csr::transpose(itf.systTran_pena[s]);
             const Csr& M = itf.inteMass[s];
             const Csr& Mp = itf.inteMass_pena[s];
             const Csr& Ii = itf.inteInpo[s];
@@ -2038,7 +1014,7 @@ void build(ddpca_mcontact& H, Problem& P) {
                 const Interface& itf = mc.searCont[sd.ts];
                 const auto& I = itf_of(sd.ts);
                 const auto& Su = H.subs[sd.sub];
-                const Csr tT = transpose(itf.systTran[sd.s]);
+                const Csr tT = csr::transpose(itf.systTran[sd.s]);
                 const Csr& Ii = itf.inteInpo[sd.s];
                 for (int64_t r = 0; r < sd.m; ++r) {
                     for (int64_t k = tT.ptr[r]; k < tT.ptr[r + 1]; ++k) rwv[sd.roff + r].push_back({Su.wcol(tT.col[k], H.oH), tT.val[k]});
@@ -3231,11 +2207,7 @@ int mcontact_gpu_create(ddpca_problem_t p, int device, int rank, int nranks, con
 }
 
 int mcontact_gpu_unique_id(void* out128) {
-    return guarded([&] {
-        ncclUniqueId id;
-        DDPCA_NCCL(ncclGetUniqueId(&id));
-        std::memcpy(out128, &id, sizeof(id));
-    });
+    return guarded([&] { rccl_unique_id(out128); });
 }
 
 int mcontact_gpu_comm_init(mcontact_t h, const void* uid) {
@@ -3245,11 +2217,7 @@ int mcontact_gpu_comm_init(mcontact_t h, const void* uid) {
         if (h->comm) throw ApiError(DDPCA_ESTATE, "handle already has a communicator");
         // nranks == 1 builds a one-rank communicator too: the MONITOR and coarse-RHS all-reduces then
         // run through RCCL on the solve stream (bit-identical to the run without one)
-        ncclUniqueId id;
-        std::memcpy(&id, uid, sizeof(id));
-        auto t = std::make_unique<RcclTransport>();
-        DDPCA_NCCL(ncclCommInitRank(&t->comm, h->nranks, id, h->rank));
-        h->comm = std::move(t);
+        h->comm = rccl_transport(h->nranks, h->rank, uid);
         coarse_invert(*h);
         prepare_graphs(*h);
     });
@@ -3263,15 +2231,8 @@ int mcontact_gpu_comm_local(mcontact_t* handles, int n) {
                 throw ApiError(DDPCA_EINVAL, "handles[r] must be rank r of n");
             if (handles[r]->comm) throw ApiError(DDPCA_ESTATE, "handle already has a communicator");
         }
-        auto hub = std::make_shared<LocalHub>();
-        hub->n = n;
-        hub->slot.resize(n);
-        for (int r = 0; r < n; ++r) {
-            auto t = std::make_unique<LocalTransport>();
-            t->hub = hub;
-            t->rank = r;
-            handles[r]->comm = std::move(t);
-        }
+        auto ts = local_transports(n);
+        for (int r = 0; r < n; ++r) handles[r]->comm = std::move(ts[r]);
         // the setup all-reduce of the coarse matrix is collective: one host thread per rank
         std::vector<std::thread> th;
         std::vector<int> rc(n, 0);
@@ -3305,7 +2266,7 @@ int mcontact_gpu_comm_loopback(mcontact_t h, ddpca_problem_t p) {
         if (C.on && !C.inverted && C.mg_gather)
             throw ApiError(DDPCA_ESTATE, "loopback: the problem must be the handle's, established in full "
                                          "(a rank-local DOUBLE_M coarse operator cannot be gathered)");
-        h->comm = std::make_unique<LoopbackTransport>();
+        h->comm = loopback_transport();
         if (C.on && !C.inverted && !C.mg) {
             // the other ranks' rows of the dense coarse operator come from the problem itself (the
             // setup all-reduce that would sum them is the identity here)
@@ -3694,76 +2655,6 @@ int ddpca_eigs_orth_bench(int device, int64_t n, int m, int reps, double* out4) 
         if (!out4) throw ApiError(DDPCA_EINVAL, "ddpca_eigs_orth_bench: NULL output");
         eigs_orth_bench(device, n, m, reps, out4);
     });
-}
-
-int ddpca_mass_solve(int device, int64_t nsys, const ddpca_csr_t* A, const double* b, double* x, double rtol,
-                     int64_t maxit, int fuse_alpha, int64_t* iters) {
-    int64_t nrow = 0;
-    std::vector<int64_t> roff;
-    std::vector<Csr> sys;
-    DevBuf<double> xd;
-    MassBatch mb;
-    hipStream_t st = nullptr;
-    auto copy_out = [&]() {  // the systems' rows of the padded batch vector, in order
-        std::vector<double> h(std::max<int64_t>(nrow, 1));
-        DDPCA_HIP(hipMemcpy(h.data(), xd.p, nrow * sizeof(double), hipMemcpyDeviceToHost));
-        int64_t o = 0;
-        for (int64_t s = 0; s < nsys; ++s) {
-            std::memcpy(x + o, h.data() + roff[s], sys[s].nrow * sizeof(double));
-            o += sys[s].nrow;
-        }
-    };
-    const int rc = guarded([&] {
-        if (nsys < 1 || !A || !b || !x || !(rtol > 0.0) || maxit < 1) throw ApiError(DDPCA_EINVAL, "ddpca_mass_solve: arguments");
-        select_device(device);
-        for (int64_t s = 0; s < nsys; ++s) {
-            const ddpca_csr_t& a = A[s];
-            if (a.nrow < 1 || a.ncol != a.nrow || !a.ptr || (a.ptr[a.nrow] > 0 && (!a.col || !a.val)))
-                throw ApiError(DDPCA_EINVAL, "ddpca_mass_solve: system " + std::to_string(s) + " is not a square CSR");
-            Csr c;
-            c.nrow = c.ncol = a.nrow;
-            c.ptr.assign(a.ptr, a.ptr + a.nrow + 1);
-            if (c.ptr[0] != 0) throw ApiError(DDPCA_EINVAL, "ddpca_mass_solve: ptr[0] != 0");
-            for (int64_t r = 0; r < a.nrow; ++r)
-                if (c.ptr[r + 1] < c.ptr[r]) throw ApiError(DDPCA_EINVAL, "ddpca_mass_solve: row pointer decreases");
-            c.col.assign(a.col, a.col + c.ptr[a.nrow]);
-            c.val.assign(a.val, a.val + c.ptr[a.nrow]);
-            bool diag = false;
-            for (int64_t r = 0; r < a.nrow; ++r)
-                for (int64_t k = c.ptr[r]; k < c.ptr[r + 1]; ++k) {
-                    if (c.col[k] < 0 || c.col[k] >= a.nrow) throw ApiError(DDPCA_EINVAL, "ddpca_mass_solve: column out of range");
-                    diag |= c.col[k] == r;
-                }
-            if (!diag) throw ApiError(DDPCA_EINVAL, "ddpca_mass_solve: a system without diagonal entries");
-            roff.push_back(nrow);
-            nrow += pad64(a.nrow);
-            sys.push_back(std::move(c));
-        }
-        std::vector<const Csr*> ptrs;
-        for (const Csr& c : sys) ptrs.push_back(&c);
-        mb.build(ptrs, roff, nrow);
-        mb.fuse_override = fuse_alpha;
-        std::vector<double> hb(nrow, 0.0);
-        int64_t o = 0;
-        for (int64_t s = 0; s < nsys; ++s) {
-            std::memcpy(hb.data() + roff[s], b + o, sys[s].nrow * sizeof(double));
-            o += sys[s].nrow;
-        }
-        DDPCA_HIP(hipMemcpy(mb.b.p, hb.data(), nrow * sizeof(double), hipMemcpyHostToDevice));
-        xd.alloc(nrow);
-        DDPCA_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        mb.solve(st, xd.p, rtol, maxit);
-        DDPCA_HIP(hipStreamSynchronize(st));
-        if (iters)
-            for (int64_t s = 0; s < nsys; ++s) iters[s] = mb.mirror.host[s].iter;
-        copy_out();
-        mb.check();  // DDPCA_ENUMERIC on a breakdown (x already copied: the last good iterate)
-    });
-    if (st) {
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamDestroy(st);
-    }
-    return rc;
 }
 
 int mcontact_gpu_destroy(mcontact_t h) {

@@ -2090,6 +2090,10 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
     if (opt.smoother < 0 || opt.smoother > 4) throw ApiError(DDPCA_EINVAL, "smoother must be 0..4");
     // the multicolour sweeps' symmetric pairing needs K = K^T: nonsymmetric handles smooth with block Jacobi
     if (opt.smoother >= 3 && general) opt.smoother = 1;
+    // (refused here, not at the first capture's launch_gs; one level has no V-cycle and no
+    // colours: the option is idle there, as smoother 3 is)
+    if (opt.smoother == 4 && opt.precond_fp32 == 0 && nlev > 1)
+        throw ApiError(DDPCA_ESTATE, "colour SSOR needs a reduced-precision V-cycle copy (precond_fp32 >= 1)");
     const bool bj = opt.smoother >= 1;
     // device numbering: perm[l][s][reference local node] = device local node.  Levels >= 1 with
     // coordinates: lexicographic, or -- table mode, when the level's distinct rows compress --
@@ -2679,7 +2683,6 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
             }
     }
     if (gs_fine() && opt.smoother == 4) {
-        if (gs.band) throw ApiError(DDPCA_EINVAL, "colour SSOR (smoother 4) on a band-mode fine level");
         gs.w.alloc(3 * lev.back().nn);
         gs.w.zero(stream);
         // the per-launch byte model in k_gs_ssor's launch order: forward colours 0..K-1 (L), backward
@@ -3530,16 +3533,13 @@ void MgpisDevice::enqueue_iteration(int prec, bool timed) {
 // graph_[prec]: iters_per_graph PCG iterations captured once and replayed; graph1_[prec]: one.
 hipGraphExec_t MgpisDevice::capture_iterations(int prec, int count, PcgScal* scp) {
     sc_cur_ = scp;
-    hipGraph_t g;
-    hipGraphExec_t ge = nullptr;
-    CaptureSection capture_section;  // device_common.hpp CaptureLock
-    DDPCA_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    for (int k = 0; k < count; ++k) enqueue_iteration(prec, false);
-    DDPCA_HIP(hipStreamEndCapture(stream, &g));
-    sc_cur_ = nullptr;
-    DDPCA_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    DDPCA_HIP(hipGraphDestroy(g));
-    return ge;
+    struct Unbind {
+        PcgScal*& p;
+        ~Unbind() { p = nullptr; }
+    } unbind{sc_cur_};  // on a throw out of the capture too
+    return capture_graph(stream, [&] {
+        for (int k = 0; k < count; ++k) enqueue_iteration(prec, false);
+    });
 }
 
 void MgpisDevice::build_graph(int prec) {

@@ -711,7 +711,11 @@ int mcontact_gpu_destroy(mcontact_t h);
  * CG's iterations after the restart.  fuse_alpha:
  * -1 the production rule (alpha inside the update kernel up to 1024 chunks per system), 0 / 1
  * force the separate / fused alpha launch.  iters[nsys] (may be NULL).  On a breakdown (p.q <= 0
- * or not finite) the system's x is its last good iterate and the call returns DDPCA_ENUMERIC. */
+ * or not finite) the system's x is its last good iterate and the call returns DDPCA_ENUMERIC.
+ * A system s + nsys/2 handed over with the nrow and the ptr, col and val pointers of system s is
+ * kept as one matrix for both, and a batch whose whole second half repeats the first this way
+ * runs the paired kernels of the ADMM loop's fused w|v solve (one matrix stream per pair; the
+ * same bits as the unpaired form, DDPCA_MCG_PAIR=0). */
 int ddpca_mass_solve(int device, int64_t nsys, const ddpca_csr_t* A, const double* b, double* x, double rtol,
                      int64_t maxit, int fuse_alpha, int64_t* iters);
 

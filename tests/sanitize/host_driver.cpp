@@ -1,7 +1,7 @@
 // Sanitizer driver for the host C++ of libddpca_amd (SURVEY §5 "race detection / sanitizers").
 //
 // Built by tests/sanitize/Makefile from the host translation units only (capi_builder, capi_host,
-// capi_multigrid, csearch, errors, lagrange, mcontact, multigrid, multiscale, sparse, writers) with
+// capi_multigrid, csearch, errors, lagrange, mass_plan, mcontact, multigrid, multiscale, sparse, writers) with
 // -fsanitize=address,undefined; no device objects, no GPU.  It drives the setup code that produces
 // every GPU operand through the C ABI the tests use:
 //   * the problem generators (BEAM single / DD, the two-block contact frictionless and Coulomb,
@@ -14,10 +14,13 @@
 //     CONSTRAINT with nodal rotations), then as a problem subdomain;
 //   * CSEARCH's contact search and ADAPTIVE_REFINE's selection on two facing surfaces;
 //   * the result-file writers;
+//   * the surface-mass batch's host setup (mass_plan.cpp, called directly): ELL-64 packing, pair
+//     detection, spectrum bounds against a dense eigensolve, Chebyshev step counts;
 //   * the refused-argument paths (bad indices, reversed pointers) of those entry points.
 // The reference-comparison harnesses (oracle/ref_multigrid, ref_csearch, ref_refine,
 // ref_lagrange_host) are linked to the same sanitized objects by the Makefile's `ref` target.
 // Exit status 0 and no sanitizer report = clean.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -26,6 +29,7 @@
 #include <vector>
 
 #include "ddpca_amd.h"
+#include "mass_plan.hpp"
 
 namespace {
 
@@ -415,6 +419,125 @@ void run_writers() {
     std::printf("{\"case\": \"writers\"}\n");
 }
 
+// a surface-mass-like SPD system: the 9-point lattice mass matrix kron(T, T), T = tridiag(1, 4, 1) / 6,
+// cut to n rows and scaled on both sides by a positive diagonal in [0.5, 2]
+ddpca::Csr mass_like(int64_t n, double seed) {
+    const int64_t m = (int64_t)std::ceil(std::sqrt((double)n));
+    auto t = [](int64_t a, int64_t b) { return a == b ? 4.0 / 6.0 : 1.0 / 6.0; };
+    auto d = [&](int64_t i) { return 1.25 + 0.75 * std::sin(seed + 1.7 * (double)i); };
+    ddpca::Csr A;
+    A.nrow = A.ncol = n;
+    A.ptr.assign(1, 0);
+    for (int64_t r = 0; r < n; ++r) {
+        const int64_t i = r / m, j = r % m;
+        for (int64_t i2 = std::max<int64_t>(i - 1, 0); i2 <= std::min(i + 1, m - 1); ++i2)
+            for (int64_t j2 = std::max<int64_t>(j - 1, 0); j2 <= std::min(j + 1, m - 1); ++j2) {
+                const int64_t c = i2 * m + j2;
+                if (c >= n) continue;
+                A.col.push_back((int32_t)c);
+                A.val.push_back(d(r) * t(i, i2) * t(j, j2) * d(c));
+            }
+        A.ptr.push_back((int64_t)A.col.size());
+    }
+    return A;
+}
+
+// eigenvalue range of D^-1/2 M D^-1/2 (= that of D^-1 M) by cyclic Jacobi rotations, dense
+void dense_spectrum(const ddpca::Csr& M, double* lmin, double* lmax) {
+    const int64_t n = M.nrow;
+    std::vector<double> S((size_t)n * n, 0.0), dg(n, 0.0);
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t k = M.ptr[r]; k < M.ptr[r + 1]; ++k)
+            if (M.col[k] == r) dg[r] = M.val[k];
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t k = M.ptr[r]; k < M.ptr[r + 1]; ++k) S[r * n + M.col[k]] = M.val[k] / std::sqrt(dg[r] * dg[M.col[k]]);
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        double offd = 0.0;
+        for (int64_t p = 0; p < n; ++p)
+            for (int64_t q = p + 1; q < n; ++q) offd += S[p * n + q] * S[p * n + q];
+        if (offd < 1e-28) break;
+        for (int64_t p = 0; p < n; ++p)
+            for (int64_t q = p + 1; q < n; ++q) {
+                if (S[p * n + q] == 0.0) continue;
+                const double th = (S[q * n + q] - S[p * n + p]) / (2.0 * S[p * n + q]);
+                const double tt = (th >= 0.0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
+                const double c = 1.0 / std::sqrt(tt * tt + 1.0), s = tt * c;
+                for (int64_t k = 0; k < n; ++k) {  // columns p, q, then rows p, q
+                    const double a = S[k * n + p], b = S[k * n + q];
+                    S[k * n + p] = c * a - s * b;
+                    S[k * n + q] = s * a + c * b;
+                }
+                for (int64_t k = 0; k < n; ++k) {
+                    const double a = S[p * n + k], b = S[q * n + k];
+                    S[p * n + k] = c * a - s * b;
+                    S[q * n + k] = s * a + c * b;
+                }
+            }
+    }
+    *lmin = *lmax = S[0];
+    for (int64_t i = 0; i < n; ++i) *lmin = std::min(*lmin, S[i * n + i]), *lmax = std::max(*lmax, S[i * n + i]);
+}
+
+// MassBatch's host setup (mass_plan.cpp) on the paired batch [A0, A1, A0, A1] of 37 and 200 rows:
+// one chunk and four, both with a ragged last chunk, 640 padded rows, R = 320
+void run_mass_plan() {
+    auto check = [](bool good, const char* what) {
+        if (!good) {
+            std::fprintf(stderr, "FAIL mass_plan: %s\n", what);
+            ++g_fail;
+        }
+    };
+    const ddpca::Csr A0 = mass_like(37, 0.3), A1 = mass_like(200, 1.1), B0 = A0, B1 = A1;
+    const std::vector<const ddpca::Csr*> A = {&A0, &A1, &A0, &A1};
+    const std::vector<int64_t> roff = {0, 64, 320, 384};
+    const int64_t nrow = 640;
+    const ddpca::MassPlan P = ddpca::mass_plan(A, roff, nrow, true);
+    check(P.nch == 10 && P.paired && P.cheb, "10 chunks, paired, Chebyshev bounds");
+    check(!ddpca::mass_plan({&A0, &A1, &B0, &B1}, roff, nrow, false).paired, "distinct copies do not pair");
+    // the packed product against the CSR product, slot order = entry order: equal exactly
+    std::vector<double> x(nrow), y(nrow, 0.0);
+    for (int64_t i = 0; i < nrow; ++i) x[i] = std::sin(0.37 * (double)i) + 0.1 * std::cos(5.1 * (double)i);
+    for (size_t s = 0; s < A.size(); ++s)
+        for (int64_t r = 0; r < A[s]->nrow; ++r)
+            for (int64_t k = A[s]->ptr[r]; k < A[s]->ptr[r + 1]; ++k) y[roff[s] + r] += A[s]->val[k] * x[roff[s] + A[s]->col[k]];
+    bool same = true, dinv = true;
+    for (int64_t g = 0; g < nrow; ++g) {
+        const int64_t c = g / 64, lane = g % 64;
+        double sum = 0.0;
+        for (int64_t q = P.off[c]; q < P.off[c] + P.slots[c]; ++q) sum += P.val[q * 64 + lane] * x[P.col[q * 64 + lane]];
+        same = same && sum == y[g];
+    }
+    for (size_t s = 0; s < A.size(); ++s)
+        for (int64_t r = 0; r < A[s]->nrow; ++r)
+            for (int64_t k = A[s]->ptr[r]; k < A[s]->ptr[r + 1]; ++k)
+                if (A[s]->col[k] == r) dinv = dinv && P.dinv[roff[s] + r] == 1.0 / A[s]->val[k];
+    check(same, "ELL product equals the CSR product");
+    check(dinv, "D^-1");
+    check(P.cb == std::vector<int64_t>({0, 1, 5, 6, 10}) && P.csys == std::vector<int32_t>({0, 1, 1, 1, 1, 2, 3, 3, 3, 3}),
+          "chunk bounds and systems");
+    // [lam_lo, lam_hi] brackets the spectrum of D^-1 M (the 37-row system, dense)
+    double lmin = 0.0, lmax = 0.0;
+    dense_spectrum(A0, &lmin, &lmax);
+    check(P.lam_lo[0] > 0.0 && P.lam_lo[0] <= lmin && lmax <= P.lam_hi[0], "bounds bracket the 37-row spectrum");
+    check(P.lam_lo[2] == P.lam_lo[0] && P.lam_hi[2] == P.lam_hi[0], "twins share their bounds");
+    // step counts: K = ceil(ln(4 sqrt(kappa) / rtol) / ln sigma), sigma = (sqrt(kappa) + 1) / (sqrt(kappa) - 1)
+    const double rtol = 1.0e-14;
+    const ddpca::ChebPlan C = ddpca::cheb_plan(P.lam_lo, P.lam_hi, rtol);
+    int64_t K = 0;
+    bool steps = C.ks.size() == A.size();
+    for (size_t s = 0; steps && s < A.size(); ++s) {
+        const double sk = std::sqrt(P.lam_hi[s] / P.lam_lo[s]);
+        const int64_t ks = std::max<int64_t>(1, (int64_t)std::ceil(std::log(4.0 * sk / rtol) / std::log((sk + 1.0) / (sk - 1.0))));
+        steps = C.ks[s] == ks;
+        K = std::max(K, ks);
+    }
+    check(steps && C.K == K, "Chebyshev step counts");
+    check(K <= ddpca::kChebMax && C.coef.size() == (size_t)(2 * K) * A.size() && C.ith.size() == A.size(), "coefficients");
+    check(ddpca::cheb_plan(P.lam_lo, P.lam_hi, 1.0e-300).coef.empty(), "no coefficients past kChebMax steps");
+    std::printf("{\"case\": \"mass_plan\", \"lam\": [%.6f, %.6f], \"dense\": [%.6f, %.6f], \"steps\": %lld}\n", P.lam_lo[0],
+                P.lam_hi[0], lmin, lmax, (long long)K);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -449,6 +572,7 @@ int main(int argc, char** argv) {
     run_octree();
     run_csearch();
     run_writers();
+    run_mass_plan();
     std::printf("{\"ok\": %s, \"failures\": %d}\n", g_fail ? "false" : "true", g_fail);
     return g_fail ? 1 : 0;
 }

@@ -222,7 +222,7 @@ def test_schedule_variants_are_bit_identical(ddpca, gpu, monkeypatch, env, opts)
     the body-balance batch and of the mass CG (MgpisDevice / MassBatch ::set_split, default on)
     against one stream, on both option sets; whole-replay pacing to the end of every solve
     against the one-iteration tail graphs; and the fused interface update's mass SpMV reading each
-    shared inteMass once for both its systems (k_mcg_spmv2) against one read per system.  ADMM trajectory, displacements and PCG iteration
+    shared inteMass once for both its systems (k_mcg_spmv<true>, device_mass.hip) against one read per system.  ADMM trajectory, displacements and PCG iteration
     counts equal bit for bit (8 ADMM iterations, reduced chain).  (The variants measured slower
     and kept opt-in in round 3 -- stencil-coded copies, XCD-slab placement, four-wave colour
     workgroups, inverses by row, fused first sweeps -- were deleted in round 4)"""

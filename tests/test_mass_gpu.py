@@ -1,4 +1,4 @@
-"""The batched surface-mass solver of the ADMM loop (MassBatch; the reference's interface mass
+"""The batched surface-mass solver of the ADMM loop (MassBatch, device_mass.hip; the reference's interface mass
 solves, MCONTACT.h:2671-2704: SimplicialLDLT below 120000 rows, 838-847, Eigen CG above,
 2680-2682) on its own through ddpca_mass_solve, and its two forms of the CG step length: alpha
 summed inside the update kernel (k_mcg_axpy_fa, the default up to 1024 chunks per system) and the
@@ -102,6 +102,38 @@ def test_mass_solve_chebyshev_start(ddpca, gpu, monkeypatch):
     with pytest.raises(ddpca.DdpcaError) as ei:
         ddpca.mass_solve([A[0], bad], np.concatenate([b[:37], [1.0, -1.0]]))
     assert ei.value.code == -6
+
+
+@pytest.mark.parametrize("fa", [0, 1], ids=["separate-alpha", "fused-alpha"])
+@pytest.mark.parametrize("cheb", ["0", "1"], ids=["cg", "chebyshev"])
+def test_mass_solve_paired_batch_is_bit_identical(ddpca, gpu, monkeypatch, cheb, fa):
+    """The paired kernels (k_mcg_spmv<true>, k_mcheb_step<true>: one matrix stream for system s and
+    its twin s + nsys/2) reached directly: [A0, A1, A0, A1] with the same two scipy objects in both
+    halves, 37 rows (one ragged chunk) and 200 rows (four chunks, the last ragged), 640 padded rows,
+    R = 320.  System 2's right-hand side is zero, so it is done at init while its twin runs; system
+    3's is system 1's times 1e3 plus noise, so those twins stop on their own.  Bit for bit and
+    iteration for iteration the same as the unpaired launch (DDPCA_MCG_PAIR=0) and as the batch of
+    four distinct copies (which never pairs); each within 1e-10 of scipy's direct solve."""
+    monkeypatch.setenv("DDPCA_MASS_CHEB", cheb)
+    A0, A1 = _mass_like(37, 20251101), _mass_like(200, 20251102)
+    rng = np.random.default_rng(13)
+    b0, b1 = rng.standard_normal(37), rng.standard_normal(200)
+    rhs = [b0, b1, np.zeros(37), 1e3 * b1 + rng.standard_normal(200)]
+    b = np.concatenate(rhs)
+    systems = [A0, A1, A0, A1]
+    x, its = ddpca.mass_solve(systems, b, fuse_alpha=fa)
+    monkeypatch.setenv("DDPCA_MCG_PAIR", "0")
+    xu, itu = ddpca.mass_solve(systems, b, fuse_alpha=fa)
+    monkeypatch.delenv("DDPCA_MCG_PAIR")
+    xc, itc = ddpca.mass_solve([m.copy() for m in systems], b, fuse_alpha=fa)
+    print("iterations", list(its))
+    assert np.array_equal(x, xu) and np.array_equal(its, itu)
+    assert np.array_equal(x, xc) and np.array_equal(its, itc)
+    o = 0
+    for m, bk in zip(systems, rhs):
+        xr = spla.spsolve(m.tocsc(), bk)
+        assert np.linalg.norm(x[o:o + len(bk)] - xr) <= 1e-10 * np.linalg.norm(xr), o
+        o += len(bk)
 
 
 def test_admm_trajectory_fused_vs_separate_alpha(ddpca, gpu, monkeypatch):

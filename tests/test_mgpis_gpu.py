@@ -244,6 +244,22 @@ def test_colour_ssor_keeps_the_solution(ddpca, gpu, lowp):
         assert np.linalg.norm(x4 - x3) <= 1e-10 * np.linalg.norm(x3)
 
 
+def test_colour_ssor_without_reduced_copy_is_refused_at_create(ddpca, gpu):
+    """smoother = 4 sweeps the reduced-precision V-cycle copy's chunk-ordered inverses, so with
+    precond_fp32 = 0 the create is refused (DDPCA_ESTATE, -4) -- by the constructor's option checks,
+    before any capture begins.  The refusal leaves nothing behind on the thread: a valid create
+    right after it captures its graphs and solves to the usual tolerance."""
+    g = golden("beam_s1")
+    P = _problem(ddpca, "beam_s1")
+    with pytest.raises(ddpca.DdpcaError) as ei:
+        ddpca.MGPIS.from_problem(P, 0, smoother=4, nu=2, precond_fp32=0)
+    assert ei.value.code == -4, ei.value
+    assert "colour SSOR" in str(ei.value)
+    x, it, rr = ddpca.MGPIS.from_problem(P, 0, smoother=3, nu=2).CG_SOLV(1, P.grid(0).consForc)
+    assert rr <= 1e-14
+    assert np.linalg.norm(x - g["x_mg"]) <= 1e-8 * np.linalg.norm(g["x_mg"])
+
+
 def test_int8_smoother_copy_keeps_the_solution(ddpca, gpu):
     """precond_fp32 = 3: the fine levels' V-cycle copies in block-scaled int8 (nine int8 and a
     scale per 3x3 block) instead of block-exponent fp16.  The Krylov operator and the stop rule stay fp64:

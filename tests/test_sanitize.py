@@ -5,7 +5,8 @@ produces every GPU operand: generators, MCONTACT::ESTABLISH's mortar operators, 
 pipeline on any octree, both coarse spaces, CSEARCH, CURVEDS/REFINE, the writers; no device code)
 with -fsanitize=address,undefined and links tests/sanitize/host_driver.cpp, which drives them through
 the C ABI (problems of every generator incl. rank-local builds, a refined curved octree, a contact
-search, the refused-argument paths).  A sanitizer report aborts the driver (halt_on_error).  The
+search, the refused-argument paths) and, called directly, the surface-mass batch's host setup
+(mass_plan.cpp: packing, pairing, spectrum bounds, Chebyshev step counts).  A sanitizer report aborts the driver (halt_on_error).  The
 reference-comparison harnesses of the CPU tests linked to the same objects (`make ref run`:
 ref_multigrid, ref_csearch, ref_refine, ref_lagrange_host, about 5 minutes) ran clean too:
 profiles/r04_sanitize.log."""
