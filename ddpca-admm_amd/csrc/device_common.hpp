@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "mgpis_layout.hpp"  // kChunk, pad64
 
 namespace ddpca {
 
@@ -24,7 +25,6 @@ namespace ddpca {
     } while (0)
 
 constexpr int kWave = 64;      // CDNA wavefront
-constexpr int kChunk = 64;     // SELL chunk = one node row per lane of a wave
 constexpr int kBlock = 256;    // 4 waves per workgroup
 
 // Stream capture vs. synchronous HIP calls on other host threads.  ROCm 7.2 invalidated a
@@ -144,7 +144,6 @@ struct DevSpan {
 };
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
-inline int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
 inline int nb256(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }  // blocks of 256 threads
 
 // the sum over a wavefront, in every lane (xor butterfly: one fixed order)

@@ -3,22 +3,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <deque>
-#include <memory>
-#include <array>
 #include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 #include <tuple>
 #include <type_traits>
-#include <omp.h>
 #include <random>
 #include <thread>
-#include <unordered_map>
 
 #include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
@@ -92,38 +85,8 @@ __device__ __forceinline__ void apply_m(const MT* minv, int64_t row, double r0, 
     }
 }
 
-// Value layout of one slot (64 lanes x one 3x3 block) of a streamed SELL-BSR3 operator.
-// fp64, paired (DDPCA_PAIRED_VALUES = 1, default): 16-B lane loads -- four 1-KiB wave runs of
-// (v[2p], v[2p+1]), then a 512-B run of v[8]: 5 load instructions per block instead of 9, the
-// fine PCG SpMV 5-8 % faster (profiles/r01_spmv_ab.json).  fp32 keeps nine 256-B runs, one per
-// entry: its paired forms -- two 16-B quads + v[8], or four 8-B pairs + v[8] -- measured 4-13 %
-// SLOWER in the smoothing and residual kernels (profiles/r01_spmv_ab.json, _f32pairs.json).  Element (ij, lane) of slot base sb:
-//   paired fp64: sb[(ij < 8 ? 128 * (ij / 2) + 2 * lane + ij % 2 : 512 + lane)]
-//   otherwise:   sb[ij * 64 + lane]
-#ifndef DDPCA_PAIRED_VALUES
-#define DDPCA_PAIRED_VALUES 1
-#endif
-template <typename T>
-constexpr bool paired_values() { return DDPCA_PAIRED_VALUES != 0 && sizeof(T) == 8; }
+// (the value layout of a slot in each storage type, slot_elem / slot_vals: mgpis_layout.hpp)
 typedef double dbl2_t __attribute__((ext_vector_type(2)));
-
-// Block-exponent fp16 storage (T = uint16_t; precond_fp32 = 2, the fine level's V-cycle copy):
-// each 3x3 block is 2^e times nine fp16 values, e = the binary exponent of the block's largest
-// |entry| (so |values| < 1 and every entry within 2^14 of the block maximum keeps fp16's 11
-// significant bits); the record is ten halves, (v0,v1) (v2,v3) (v4,v5) (v6,v7) (v8,e), one
-// 256-B dword run per pair: a slot is 1280 B, 20 B per block against 36 B for fp32.  A block
-// and its transpose share e and round alike, so the operator stays exactly symmetric.
-//
-// Block-scaled int8 storage (T = uint8_t; precond_fp32 = 3): nine int8 values times a per-block
-// scale max|entry| / 127 kept to 16 mantissa bits (the fp32 scale's top 24 bits, the low byte of
-// its word holds q8), so the largest entry maps to 127 and every entry is within half a scale of
-// its value; the record is three 256-B dword runs per slot, (q0..q3) (q4..q7) (q8 | scale bits
-// 8..31): 12 B per block against 20 for fp16.  Symmetric as the fp16 copy (a block and its
-// transpose share the scale).  With the Krylov operator and the stop rule in fp64 only the
-// preconditioner moves: 18-19 PCG iterations per solve against 18 with the fp16 copy, the
-// headline +5.7 % (a power-of-two scale, 10 B per block, took 19-20 and +4.0 %).
-template <typename T>
-constexpr int slot_vals() { return sizeof(T) == 1 ? 12 : sizeof(T) == 2 ? 10 : 9; }
 
 // storage type of the smoother inverse on a level whose operator values are stored as T: fp64
 // with fp64 operators, fp32 on the reduced-precision levels (precond_fp32 >= 1)
@@ -134,46 +97,6 @@ __device__ __forceinline__ double h16_lo(uint32_t w) {
     return (double)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu));
 }
 __device__ __forceinline__ double h16_hi(uint32_t w) { return (double)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
-
-// host: one block (9 fp64 entries, row-major) -> the ten-half record
-inline void to_h16_block(const double* v, uint16_t* rec) {
-    double m = 0.0;
-    for (int k = 0; k < 9; ++k) m = std::max(m, std::fabs(v[k]));
-    int e = 0;
-    if (m > 0.0) std::frexp(m, &e);
-    for (int k = 0; k < 9; ++k) rec[k] = __builtin_bit_cast(uint16_t, (_Float16)std::ldexp(v[k], -e));
-    rec[9] = (uint16_t)(int16_t)e;
-}
-
-// host: one block -> the twelve-byte int8 record (nine values, then the scale's bits 8..31)
-inline bool to_q8_block(const double* v, uint8_t* rec) {
-    double m = 0.0;
-    for (int k = 0; k < 9; ++k) m = std::max(m, std::fabs(v[k]));
-    const float s32 = (float)(m / 127.0);
-    if (m > 0.0 && !(s32 > 0.0f && std::isfinite(s32) && std::isnormal(s32))) return false;
-    const uint32_t bits = __builtin_bit_cast(uint32_t, s32) & 0xFFFFFF00u;
-    const double sc = (double)__builtin_bit_cast(float, bits);
-    for (int k = 0; k < 9; ++k)
-        rec[k] = (uint8_t)(int8_t)(sc > 0.0 ? std::max(-127.0, std::min(127.0, std::nearbyint(v[k] / sc))) : 0.0);
-    rec[9] = (uint8_t)(bits >> 8);
-    rec[10] = (uint8_t)(bits >> 16);
-    rec[11] = (uint8_t)(bits >> 24);
-    return true;
-}
-
-// position of record byte k (0..11) of `lane` in a 768-B int8 slot
-inline int64_t q8_pos(int k, int64_t lane) { return 256 * (k / 4) + 4 * lane + k % 4; }
-
-// stored bytes of one 3x3 block's values in storage type vt (ValType)
-inline double vbytes(int vt) {
-    return vt == kValQ8 ? 12.0 : vt == kValH16 ? 20.0 : vt == kVal32 ? 36.0 : 72.0;
-}
-
-template <typename T>
-__host__ __device__ inline int64_t slot_elem(int ij, int64_t lane) {
-    if (!paired_values<T>()) return (int64_t)ij * kChunk + lane;
-    return ij == 8 ? 512 + lane : 128 * (ij / 2) + 2 * lane + ij % 2;
-}
 
 // x_j gathered for a block product: three fp64 values at stride 3 (three 8-B loads), or -- the
 // multicolour sweeps' fp32 iterate copy (GsFine::x4, precond_fp32 = 4) -- one 16-B load of the
@@ -1414,219 +1337,6 @@ void pinv_general_device(std::vector<double>& A, int64_t n, hipStream_t st, int6
     DDPCA_HIP(hipMemcpy(A.data(), C.p, A.size() * sizeof(double), hipMemcpyDeviceToHost));
 }
 
-bool invert3(const double m[9], double r[9]) {
-    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) +
-                       m[2] * (m[3] * m[7] - m[4] * m[6]);
-    if (!(std::abs(det) > 0.0)) return false;
-    r[0] = (m[4] * m[8] - m[5] * m[7]) / det;
-    r[1] = (m[2] * m[7] - m[1] * m[8]) / det;
-    r[2] = (m[1] * m[5] - m[2] * m[4]) / det;
-    r[3] = (m[5] * m[6] - m[3] * m[8]) / det;
-    r[4] = (m[0] * m[8] - m[2] * m[6]) / det;
-    r[5] = (m[2] * m[3] - m[0] * m[5]) / det;
-    r[6] = (m[3] * m[7] - m[4] * m[6]) / det;
-    r[7] = (m[1] * m[6] - m[0] * m[7]) / det;
-    r[8] = (m[0] * m[4] - m[1] * m[3]) / det;
-    return true;
-}
-
-constexpr int64_t kMaxRowBlocks = 128;  // longest node-block row the table mode types (longer: streamed)
-
-// Quantised (z, y, x) keys of a level's nodes: coordinates quantised to 1e-9 of the bounding
-// box, so nodes of one mesh plane share a key despite rounding in their coordinates.
-using Key3 = std::array<int64_t, 3>;
-std::vector<Key3> quantised_keys(const double* xyz, int64_t n) {
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-    for (int64_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = i ? std::min(lo[a], xyz[3 * i + a]) : xyz[3 * i + a];
-            hi[a] = i ? std::max(hi[a], xyz[3 * i + a]) : xyz[3 * i + a];
-        }
-    const double ext = std::max({hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]});
-    const double q = ext > 0.0 ? 1e-9 * ext : 1.0;
-    std::vector<Key3> key(n);
-    for (int64_t i = 0; i < n; ++i)
-        key[i] = {std::llround((xyz[3 * i + 2] - lo[2]) / q), std::llround((xyz[3 * i + 1] - lo[1]) / q),
-                  std::llround((xyz[3 * i] - lo[0]) / q)};
-    return key;
-}
-
-// Device node order of one level, p[reference node] = device node: lexicographic in (z, y, x);
-// with row types, grouped by type first (lexicographic inside a type), so 64-row chunks are
-// type-homogeneous wherever a type has enough rows.
-std::vector<int32_t> device_order(const std::vector<Key3>& key, const std::vector<int32_t>* type) {
-    const int64_t n = (int64_t)key.size();
-    std::vector<int32_t> idx(n), p(n);
-    std::iota(idx.begin(), idx.end(), 0);
-    std::stable_sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) {
-        if (type && (*type)[a] != (*type)[b]) return (*type)[a] < (*type)[b];
-        return key[a] < key[b];
-    });
-    for (int64_t k = 0; k < n; ++k) p[idx[k]] = (int32_t)k;
-    return p;
-}
-
-// Canonical slot order of row r: its blocks sorted by the neighbour's quantised offset from the
-// row node -- independent of any numbering, so equal rows stay equal after renumbering.
-void canonical_slots(const Bsr3& A, int64_t r, const std::vector<Key3>& key, int64_t* ord) {
-    const int64_t len = A.ptr[r + 1] - A.ptr[r];
-    for (int64_t t = 0; t < len; ++t) ord[t] = A.ptr[r] + t;
-    const Key3& kr = key[r];
-    std::sort(ord, ord + len, [&](int64_t u, int64_t v) {
-        const Key3& a = key[A.col[u]];
-        const Key3& b = key[A.col[v]];
-        for (int d = 0; d < 3; ++d)
-            if (a[d] - kr[d] != b[d] - kr[d]) return a[d] - kr[d] < b[d] - kr[d];
-        return false;
-    });
-}
-
-// Bit-exact row types of one level of one subdomain: masked block values in canonical slot order.
-std::vector<int32_t> row_types(const Bsr3& A, const uint8_t* fr, const std::vector<Key3>& key, int64_t& ntypes) {
-    const int64_t n = A.nb;
-    std::vector<int32_t> t(n);
-    std::unordered_map<uint64_t, std::vector<int32_t>> bucket;
-    std::vector<std::vector<double>> reps;
-    std::vector<double> v;
-    int64_t ord[128];
-    for (int64_t r = 0; r < n; ++r) {
-        const int64_t len = A.ptr[r + 1] - A.ptr[r];
-        canonical_slots(A, r, key, ord);
-        v.assign(9 * len, 0.0);
-        for (int64_t s = 0; s < len; ++s) {
-            const int64_t k = ord[s], j = A.col[k];
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b) {
-                    double x = A.val[9 * k + 3 * a + b];
-                    if (!fr[3 * r + a] || !fr[3 * j + b]) x = (j == r && a == b) ? 1.0 : 0.0;
-                    v[9 * s + 3 * a + b] = x;
-                }
-        }
-        uint64_t h = 1469598103934665603ull ^ (uint64_t)len;
-        for (double x : v) {
-            uint64_t b;
-            std::memcpy(&b, &x, 8);
-            h = (h ^ b) * 1099511628211ull;
-            h ^= h >> 29;
-        }
-        auto& cand = bucket[h];
-        int32_t id = -1;
-        for (int32_t c : cand)
-            if (reps[c].size() == v.size() && std::memcmp(reps[c].data(), v.data(), v.size() * sizeof(double)) == 0) {
-                id = c;
-                break;
-            }
-        if (id < 0) {
-            id = (int32_t)reps.size();
-            cand.push_back(id);
-            reps.push_back(v);
-        }
-        t[r] = id;
-    }
-    ntypes = (int64_t)reps.size();
-    return t;
-}
-
-// Table mode of one level: every row's values (device slot order, masks applied, zero beyond the
-// row) are deduplicated bit-exactly, per subdomain in parallel, then merged into one table.  Used
-// when the table is at most a fifth of the streamed values (or when forced, for tests).
-void build_table(LevelDev& L, const std::vector<int32_t>& slots, const std::vector<int64_t>& off,
-                 const std::vector<double>& val, bool force) {
-    int64_t tmax = 0;
-    for (int32_t s : slots) tmax = std::max<int64_t>(tmax, s);
-    const int64_t ts9 = std::max<int64_t>(tmax * 9, 1);
-    const int nsub = (int)L.noff.size();
-    std::vector<std::vector<double>> subtab(nsub);
-    std::vector<int32_t> rt(L.nn, 0);
-#pragma omp parallel for schedule(dynamic, 1)
-    for (int s = 0; s < nsub; ++s) {
-        std::unordered_map<uint64_t, std::vector<int32_t>> bucket;
-        std::vector<double>& T = subtab[s];
-        std::vector<double> rowv(ts9);
-        int32_t nt = 0;
-        for (int64_t g = L.noff[s]; g < L.noff[s] + pad64(L.nloc[s]); ++g) {
-            const int64_t c = g / kChunk, lane = g % kChunk;
-            std::fill(rowv.begin(), rowv.end(), 0.0);
-            for (int64_t t = 0; t < slots[c]; ++t)
-                for (int ij = 0; ij < 9; ++ij) rowv[t * 9 + ij] = val[((off[c] + t) * 9 + ij) * kChunk + lane];
-            uint64_t h = 1469598103934665603ull;
-            for (double v : rowv) {
-                uint64_t b;
-                std::memcpy(&b, &v, 8);
-                h = (h ^ b) * 1099511628211ull;
-                h ^= h >> 29;
-            }
-            int32_t id = -1;
-            auto& cand = bucket[h];
-            for (int32_t t : cand)
-                if (std::memcmp(&T[(size_t)t * ts9], rowv.data(), ts9 * sizeof(double)) == 0) {
-                    id = t;
-                    break;
-                }
-            if (id < 0) {
-                id = nt++;
-                cand.push_back(id);
-                T.insert(T.end(), rowv.begin(), rowv.end());
-            }
-            rt[g] = id;
-        }
-    }
-    int64_t ntypes = 0;
-    std::vector<int64_t> base(nsub);
-    for (int s = 0; s < nsub; ++s) {
-        base[s] = ntypes;
-        ntypes += (int64_t)subtab[s].size() / ts9;
-    }
-    const double tab_bytes = (double)ntypes * ts9 * 8.0, val_bytes = (double)val.size() * 8.0;
-    if (!force && tab_bytes > 0.2 * val_bytes) return;
-    std::vector<double> tab;
-    tab.reserve((size_t)ntypes * ts9);
-    for (int s = 0; s < nsub; ++s) {
-        tab.insert(tab.end(), subtab[s].begin(), subtab[s].end());
-        for (int64_t g = L.noff[s]; g < L.noff[s] + pad64(L.nloc[s]); ++g) rt[g] += (int32_t)base[s];
-    }
-    // chunks whose 64 rows share one type read their table row through scalar loads
-    std::vector<int32_t> ct(L.nch);
-    int64_t uniform = 0;
-    for (int64_t c = 0; c < L.nch; ++c) {
-        ct[c] = rt[c * kChunk];
-        for (int64_t lane = 1; lane < kChunk && ct[c] >= 0; ++lane)
-            if (rt[c * kChunk + lane] != ct[c]) ct[c] = -1;
-        uniform += ct[c] >= 0;
-    }
-    L.tbl = true;
-    L.tstride = ts9;
-    L.ntypes = ntypes;
-    L.nuniform = uniform;
-    L.rtype.upload(rt);
-    L.ctype.upload(ct);
-    L.tab.upload(tab);
-}
-
-std::vector<int32_t> identity_order(int64_t n) {
-    std::vector<int32_t> p(n);
-    std::iota(p.begin(), p.end(), 0);
-    return p;
-}
-
-// Chebyshev coefficients of sweep k on [lmax/30, lmax] of M K (k = 0: the 1/theta start)
-void cheb_coef(double lmax, int k, double& c1, double& c2) {
-    const double lmin = lmax / 30.0;
-    const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sigma = theta / delta;
-    if (k == 0) {
-        c1 = 0.0;
-        c2 = 1.0 / theta;
-        return;
-    }
-    double rho_old = 1.0 / sigma, rho = rho_old;
-    for (int i = 1; i <= k; ++i) {
-        rho = 1.0 / (2.0 * sigma - rho_old);
-        if (i < k) rho_old = rho;
-    }
-    c1 = rho * rho_old;
-    c2 = 2.0 * rho / delta;
-}
-
 }  // namespace
 
 // ============================================================================== host plumbing
@@ -1702,377 +1412,81 @@ int64_t pace_until_done(hipStream_t stream, hipGraphExec_t graph, const MirrorBu
 }
 
 // ============================================================================== setup
+// What reaches the device is planned on the host in mgpis_plan.cpp; here a plan is uploaded,
+// array by array, and dropped.
 namespace {
-using KidList = std::vector<std::vector<std::pair<int32_t, double>>>;
-
-// Lattice form of a uniformly averaging transfer l-1 -> l (LevelDev::lat): accepted only when it
-// reproduces the explicit lists exactly, per subdomain: every fine node's parent set is p0 plus
-// the subset sums of three coarse strides (the differences of the two-parent nodes), every coarse
-// node's child set is its fine copy plus d . t for d in {-1,0,1}^3 (t from the half-weight
-// children) with weight 2^-|d|, the 27 offsets distinct.  Box lattices numbered lexicographically
-// (the device renumbering of levels >= 1) pass; anything else keeps the explicit lists.
-bool lattice_reject(int why) {
-    if (std::getenv("DDPCA_VERBOSE")) std::fprintf(stderr, "[ddpca] lattice transfer rejected (check %d)\n", why);
-    return false;
+// the one array of V into the buffer of its storage type
+void upload_values(const BlockValues& V, DevBuf<double>& d64, DevBuf<float>& d32, DevBuf<uint16_t>& d16, DevBuf<uint8_t>& d8) {
+    if (V.vt == kValQ8) d8.upload(V.v8);
+    else if (V.vt == kValH16) d16.upload(V.v16);
+    else if (V.vt == kVal32) d32.upload(V.v32);
+    else d64.upload(V.v64.get(), V.n);
 }
 
-bool lattice_transfer(LevelDev& L, const LevelDev& C, const std::vector<int32_t>& ppar, const KidList& kids) {
-    const size_t ns = L.noff.size();
-    std::vector<uint32_t> ppk(L.nn, 0u), rmsk(C.nn, 0u);
-    std::vector<int32_t> pstr(3 * ns, 0), rstr(3 * ns, 0), rf0(C.nn, 0);
-    if (C.nn >= (int64_t)1 << 29 || L.nn >= (int64_t)1 << 31) return lattice_reject(0);
-    auto three = [](std::vector<int64_t>& d, int32_t* out, int64_t fill) {
-        std::sort(d.begin(), d.end());
-        d.erase(std::unique(d.begin(), d.end()), d.end());
-        if (d.size() > 3 || (!d.empty() && d[0] <= 0)) return lattice_reject(1);
-        for (int k = 0; k < 3; ++k) out[k] = (int32_t)(k < (int)d.size() ? d[k] : fill + k);
-        return true;
-    };
-    for (size_t s = 0; s < ns; ++s) {
-        // prolongation
-        std::vector<int64_t> d;
-        int32_t P[8];
-        auto parents = [&](int64_t gf) {
-            int np = 0;
-            while (np < 8 && ppar[np * L.nn + gf] >= 0) {
-                P[np] = ppar[np * L.nn + gf];
-                ++np;
-            }
-            std::sort(P, P + np);
-            return np;
-        };
-        const int64_t f_lo = L.noff[s], f_hi = f_lo + L.nloc[s];
-        for (int64_t gf = f_lo; gf < f_hi; ++gf)
-            if (parents(gf) == 2) d.push_back((int64_t)P[1] - P[0]);
-        int32_t* st = &pstr[3 * s];
-        if (!three(d, st, (int64_t)1 << 28)) return lattice_reject(2);
-        for (int64_t gf = f_lo; gf < f_hi; ++gf) {
-            const int np = parents(gf);
-            if (np != 1 && np != 2 && np != 4 && np != 8) return lattice_reject(3);
-            bool found = false;
-            for (uint32_t code = 0; code < 8 && !found; ++code) {
-                if ((1 << __builtin_popcount(code)) != np) continue;
-                int64_t set[8];
-                int m = 0;
-                for (uint32_t q = 0; q < 8; ++q)
-                    if ((q & ~code) == 0)
-                        set[m++] = P[0] + ((q & 1) ? st[0] : 0) + ((q & 2) ? st[1] : 0) + ((q & 4) ? (int64_t)st[2] : 0);
-                std::sort(set, set + m);
-                bool eq = true;
-                for (int k = 0; k < m; ++k) eq &= set[k] == P[k];
-                if (eq) {
-                    ppk[gf] = (uint32_t)P[0] | (code << 29);
-                    found = true;
-                }
-            }
-            if (!found) return lattice_reject(4);
-        }
-        // restriction
-        const int64_t c_lo = C.noff[s], c_hi = c_lo + C.nloc[s];
-        d.clear();
-        for (int64_t j = c_lo; j < c_hi; ++j) {
-            if (kids[j].empty() || kids[j][0].second != 1.0) return lattice_reject(5);
-            for (const auto& k : kids[j])
-                if (k.second == 0.5) d.push_back(std::abs((int64_t)k.first - kids[j][0].first));
-        }
-        int32_t* t = &rstr[3 * s];
-        if (!three(d, t, (int64_t)1 << 29)) return lattice_reject(6);
-        std::vector<std::pair<int64_t, int>> offs;  // offset -> bit
-        for (int q = 0; q < 27; ++q)
-            offs.push_back({(int64_t)(q % 3 - 1) * t[0] + (int64_t)((q / 3) % 3 - 1) * t[1] + (int64_t)(q / 9 - 1) * t[2], q});
-        std::sort(offs.begin(), offs.end());
-        for (int q = 1; q < 27; ++q)
-            if (offs[q].first == offs[q - 1].first) return lattice_reject(7);
-        for (int64_t j = c_lo; j < c_hi; ++j) {
-            const int64_t f0 = kids[j][0].first;
-            uint32_t msk = 0;
-            for (const auto& k : kids[j]) {
-                const int64_t o = (int64_t)k.first - f0;
-                auto it = std::lower_bound(offs.begin(), offs.end(), std::make_pair(o, -1));
-                if (it == offs.end() || it->first != o) return lattice_reject(8);
-                const int q = it->second;
-                const int nz = (q % 3 != 1) + ((q / 3) % 3 != 1) + (q / 9 != 1);
-                if (k.second != 1.0 / (double)(1 << nz) || ((msk >> q) & 1u)) return lattice_reject(9);
-                msk |= 1u << q;
-            }
-            rmsk[j] = msk;
-            rf0[j] = (int32_t)f0;
-        }
+// shape, SELL index arrays and table of a level (its values follow, copy by copy)
+void upload_index(LevelDev& L, const LevelPlan& P) {
+    static_cast<LevelShape&>(L) = P;
+    L.slots.upload(P.slots);
+    L.csub.upload(P.csub);
+    L.off.upload(P.off);
+    L.col.upload(P.col);
+    if (!P.col16.empty()) L.col16.upload(P.col16);
+    if (P.tbl) {
+        L.rtype.upload(P.rtype);
+        L.ctype.upload(P.ctype);
+        L.tab.upload(P.tab);
     }
-    L.lat = true;
-    L.uw = true;
-    L.ppk.upload(ppk);
-    L.pstr.upload(pstr);
-    L.rmsk.upload(rmsk);
-    L.rf0.upload(rf0);
-    L.rstr.upload(rstr);
-    return true;
 }
 
-// The fine level's colour structure (GsFine) from its host SELL arrays (col: batch device
-// columns, val: masked fp64 blocks val[(q * 9 + ij) * 64 + lane]); vt: the V-cycle copy's type.
-// A colour's rows go to chunks in device order, i.e. along the x lines of a box (16 x 16-node
-// tiles of one plane measured 1.8 % slower at the headline, profiles/r03i).
-// band (optional, per device node of the level): colour and sweep only the flagged rows; the others
-// go to the ring group (a flagged neighbour) or the far group (none) -- GsFine::band
-void build_gs(GsFine& G, const LevelDev& L, int nsub, const std::vector<int64_t>& off, const std::vector<int32_t>& col,
-              const std::vector<double>& val, int vt, const std::vector<uint8_t>* band = nullptr) {
-    // greedy colouring in device order, per member
-    std::vector<int8_t> colour(L.nn, -1);
-    std::vector<int> ncol_sub(nsub, 0);
-    int too_many = 0;
-#pragma omp parallel for schedule(dynamic, 1) reduction(max : too_many)
-    for (int s = 0; s < nsub; ++s) {
-        for (int64_t g = L.noff[s]; g < L.noff[s] + L.nloc[s]; ++g) {
-            if (band && !(*band)[g]) continue;
-            const int64_t c = g / kChunk, lane = g % kChunk;
-            uint64_t used = 0;
-            for (int64_t q = off[c]; q < off[c + 1]; ++q) {
-                const int64_t j = col[q * kChunk + lane];
-                if (j != g && colour[j] >= 0) used |= 1ull << colour[j];
-            }
-            if (used == ~0ull) {
-                too_many = 1;
-                break;
-            }
-            const int k = __builtin_ctzll(~used);
-            colour[g] = (int8_t)k;
-            ncol_sub[s] = std::max(ncol_sub[s], k + 1);
-        }
+void upload_colours(GsFine& G, const ColourPlan& P) {
+    static_cast<ColourShape&>(G) = P;
+    if (!P.minvc.empty()) G.minvc.upload(P.minvc);
+    G.list.upload(P.list);
+    G.rowidx.upload(P.rowidx);
+    G.csub.upload(P.csub);
+    G.nsl.upload(P.nsl);
+    G.nsu.upload(P.nsu);
+    G.offl.upload(P.offl);
+    G.offu.upload(P.offu);
+    G.cb.upload(P.cb);
+    if (!P.col16.empty()) G.col16.upload(P.col16);
+    else G.col.upload(P.col);
+    upload_values(P.val, G.val64, G.val32, G.val16, G.val8);
+}
+
+void upload_transfer(LevelDev& L, const TransferPlan& T) {
+    static_cast<TransferShape&>(L) = T;
+    if (T.nrot) {
+        L.rot_row.upload(T.rot_row);
+        L.rot_ptr.upload(T.rot_ptr);
+        L.rot_par.upload(T.rot_par);
+        L.rot_blk.upload(T.rot_blk);
+        L.rotc_row.upload(T.rotc_row);
+        L.rotc_ptr.upload(T.rotc_ptr);
+        L.rotc_kid.upload(T.rotc_kid);
+        L.rotc_blk.upload(T.rotc_blk);
     }
-    if (too_many) throw ApiError(DDPCA_EINVAL, "multicolour smoother: a node graph needing more than 64 colours");
-    const int K = *std::max_element(ncol_sub.begin(), ncol_sub.end());
-    // chunk groups per member: the colours, then (band mode) the ring and the far rows
-    const int KG = band ? K + 2 : K;
-    auto is_band = [&](int64_t j) { return colour[j] >= 0; };
-    // colour chunks, member-major and colour-minor
-    std::vector<std::vector<int64_t>> rows((size_t)nsub * KG);
-    for (int s = 0; s < nsub; ++s)
-        for (int64_t g = L.noff[s]; g < L.noff[s] + L.nloc[s]; ++g) {
-            int grp = colour[g];
-            if (grp < 0) {
-                grp = K + 1;  // far unless a neighbour is in the band
-                const int64_t nc = g / kChunk, lane = g % kChunk;
-                for (int64_t q = off[nc]; q < off[nc + 1] && grp == K + 1; ++q) {
-                    const int64_t j = col[q * kChunk + lane];
-                    if (j != g && is_band(j)) grp = K;
-                }
-            }
-            rows[(size_t)s * KG + grp].push_back(g);
-        }
-    // which neighbours a row of group k stores: colours L = earlier colours and every non-band
-    // column (x = 0 there in the forward sweep), U = the rest; ring rows: their band columns as L
-    auto store = [&](int k, int64_t j) -> int {  // 0 L, 1 U, -1 not stored
-        if (k < K) return colour[j] < k ? 0 : 1;
-        if (k == K) return is_band(j) ? 0 : -1;
-        return -1;
-    };
-    std::vector<int32_t> rowidx, csub, nsl, nsu;
-    std::vector<int64_t> offl, offu, cb(nsub + 1, 0);
-    std::vector<std::vector<int32_t>> bycol(KG);
-    std::vector<int64_t> base;  // first row of each chunk in its (s, k) list
-    std::vector<size_t> lists;
-    G.nnzb_sub.assign(nsub, 0);
-    G.slots_sub.assign(nsub, 0);
-    G.band = band != nullptr;
-    G.band_rows_sub.assign(nsub, 0);
-    G.ring_rows_sub.assign(nsub, 0);
-    G.far_rows_sub.assign(nsub, 0);
-    G.ring_nnzb_sub.assign(nsub, 0);
-    for (int s = 0; s < nsub; ++s) {
-        cb[s] = (int64_t)csub.size();
-        for (int k = 0; k < KG; ++k) {
-            const auto& R = rows[(size_t)s * KG + k];
-            (k < K ? G.band_rows_sub : k == K ? G.ring_rows_sub : G.far_rows_sub)[s] += (int64_t)R.size();
-            for (size_t r0 = 0; r0 < R.size(); r0 += kChunk) {
-                const int64_t c = (int64_t)csub.size();
-                bycol[k].push_back((int32_t)c);
-                csub.push_back(s);
-                base.push_back((int64_t)r0);
-                lists.push_back((size_t)s * KG + k);
-                int32_t ml = 0, mu = 0;
-                for (size_t i = r0; i < std::min(R.size(), r0 + kChunk); ++i) {
-                    const int64_t g = R[i], nc = g / kChunk, lane = g % kChunk;
-                    int32_t nl = 0, nu = 0;
-                    for (int64_t q = off[nc]; q < off[nc + 1]; ++q) {
-                        const int64_t j = col[q * kChunk + lane];
-                        if (j == g) continue;
-                        const int t = store(k, j);
-                        if (t == 0) ++nl;
-                        else if (t == 1) ++nu;
-                    }
-                    ml = std::max(ml, nl);
-                    mu = std::max(mu, nu);
-                    (k < K ? G.nnzb_sub : G.ring_nnzb_sub)[s] += nl + nu;
-                }
-                nsl.push_back(ml);
-                nsu.push_back(mu);
-            }
-        }
+    if (T.lat) {
+        L.ppk.upload(T.ppk);
+        L.pstr.upload(T.pstr);
+        L.rmsk.upload(T.rmsk);
+        L.rf0.upload(T.rf0);
+        L.rstr.upload(T.rstr);
+        return;
     }
-    const int64_t nch = (int64_t)csub.size();
-    cb[nsub] = nch;
-    // slots per chunk: the longest row's L and U counts
-    int64_t nslot = 0;
-    for (int64_t c = 0; c < nch; ++c) {
-        offl.push_back(nslot);
-        offu.push_back(nslot + nsl[c]);
-        nslot += nsl[c] + nsu[c];
-        G.slots_sub[csub[c]] += nsl[c] + nsu[c];
-    }
-    rowidx.assign(nch * kChunk, 0);
-    const bool c16 = L.col16.p != nullptr;
-    std::vector<int32_t> gcol(c16 ? 0 : std::max<int64_t>(nslot * kChunk, 1), 0);
-    std::vector<int16_t> gcol16(c16 ? std::max<int64_t>(nslot * kChunk, 1) : 0, 0);
-    const int nv = vt == kValQ8 ? 12 : vt == kValH16 ? 10 : 9;
-    std::vector<uint16_t> v16(vt == kValH16 ? std::max<int64_t>(nslot * nv * kChunk, 1) : 0, 0);
-    std::vector<uint8_t> v8(vt == kValQ8 ? std::max<int64_t>(nslot * nv * kChunk, 1) : 0, 0);
-    std::atomic<bool> q8_ok{true};  // written from the omp loop below
-    std::vector<float> v32(vt == kVal32 ? std::max<int64_t>(nslot * nv * kChunk, 1) : 0, 0.0f);
-    std::vector<double> v64(vt == kVal64 ? std::max<int64_t>(nslot * nv * kChunk, 1) : 0, 0.0);
-#pragma omp parallel for schedule(dynamic, 64)
-    for (int64_t c = 0; c < nch; ++c) {
-        const auto& R = rows[lists[c]];
-        const int k = (int)(lists[c] % KG);
-        const int64_t r0 = base[c], nr = std::min<int64_t>(kChunk, (int64_t)R.size() - r0);
-        for (int64_t lane = 0; lane < kChunk; ++lane) {
-            const bool real = lane < nr;
-            const int64_t g = real ? R[r0 + lane] : R[r0];
-            rowidx[c * kChunk + lane] = real ? (int32_t)g : ~(int32_t)g;
-            // pad slots: the row itself (offset 0), zero blocks
-            for (int64_t q = offl[c]; q < offl[c] + nsl[c] + nsu[c]; ++q) {
-                if (c16) gcol16[q * kChunk + lane] = 0;
-                else gcol[q * kChunk + lane] = (int32_t)g;
-            }
-            if (!real) continue;
-            const int64_t nc = g / kChunk, nl = g % kChunk;
-            int64_t ql = offl[c], qu = offu[c];
-            for (int64_t q = off[nc]; q < off[nc + 1]; ++q) {
-                const int64_t j = col[q * kChunk + nl];
-                if (j == g) continue;
-                const int st = store(k, j);
-                if (st < 0) continue;
-                const int64_t t = st == 0 ? ql++ : qu++;
-                if (c16) gcol16[t * kChunk + lane] = (int16_t)(j - g);
-                else gcol[t * kChunk + lane] = (int32_t)j;
-                double blk[9];
-                for (int ij = 0; ij < 9; ++ij) blk[ij] = val[(q * 9 + ij) * kChunk + nl];
-                if (vt == kValH16) {
-                    uint16_t rec[10];
-                    to_h16_block(blk, rec);
-                    for (int e = 0; e < 10; ++e) v16[t * 10 * kChunk + 128 * (e / 2) + 2 * lane + e % 2] = rec[e];
-                } else if (vt == kValQ8) {
-                    uint8_t rec[12];
-                    if (!to_q8_block(blk, rec)) q8_ok.store(false, std::memory_order_relaxed);
-                    for (int e = 0; e < 12; ++e) v8[t * 12 * kChunk + q8_pos(e, lane)] = rec[e];
-                } else if (vt == kVal32) {
-                    for (int ij = 0; ij < 9; ++ij) v32[t * 9 * kChunk + slot_elem<float>(ij, lane)] = (float)blk[ij];
-                } else {
-                    for (int ij = 0; ij < 9; ++ij) v64[t * 9 * kChunk + slot_elem<double>(ij, lane)] = blk[ij];
-                }
-            }
-        }
-    }
-    // per-launch byte model: a block's stored value record + its column entry, per real row b, the
-    // fp32 inverse, x or r written and the row index, and every distinct x entry the launch
-    // gathers (forward colour k: rows of earlier colours; residual: later ones; backward: all
-    // other colours) once
-    {
-        if (!q8_ok) throw ApiError(DDPCA_EINVAL, "block-scaled int8 copy: a block's scale is out of fp32's normal range");
-        const double vb = vbytes(vt) + (c16 ? 2.0 : 4.0);
-        const double rowf = 24.0 + (vt == kVal64 ? 72.0 : 36.0) + 24.0 + 4.0;
-        std::vector<double> nl_k(K, 0.0), nu_k(K, 0.0), rows_k(K, 0.0), gx_f(K, 0.0), gx_b(K, 0.0);
-        double gx_r = 0.0;
-        std::vector<int32_t> seen_f(L.nn, -1), seen_b(L.nn, -1), seen_r(L.nn, 0), seen_u(L.nn, -1), seen_l(L.nn, 0);
-        std::vector<double> gx_u(K, 0.0);
-        double gx_l = 0.0;
-        for (int k = 0; k < K; ++k)
-            for (int s = 0; s < nsub; ++s)
-                for (int64_t g : rows[(size_t)s * KG + k]) {
-                    rows_k[k] += 1.0;
-                    const int64_t nc = g / kChunk, lane = g % kChunk;
-                    for (int64_t q = off[nc]; q < off[nc + 1]; ++q) {
-                        const int64_t j = col[q * kChunk + lane];
-                        if (j == g) continue;
-                        if (colour[j] < k) {
-                            nl_k[k] += 1.0;
-                            if (seen_f[j] != k) seen_f[j] = k, gx_f[k] += 1.0;
-                            if (!seen_l[j]) seen_l[j] = 1, gx_l += 1.0;
-                        } else {
-                            nu_k[k] += 1.0;
-                            if (!seen_r[j]) seen_r[j] = 1, gx_r += 1.0;
-                            if (seen_u[j] != k) seen_u[j] = k, gx_u[k] += 1.0;
-                        }
-                        if (seen_b[j] != k) seen_b[j] = k, gx_b[k] += 1.0;
-                    }
-                }
-        G.launch_bytes.clear();
-        double res = 0.0;
-        for (int k = 0; k < K; ++k) {
-            G.launch_bytes.push_back(vb * nl_k[k] + rowf * rows_k[k] + 24.0 * gx_f[k]);
-            res += vb * nu_k[k] + 28.0 * rows_k[k];
-        }
-        G.launch_bytes.push_back(res + 24.0 * gx_r);
-        for (int k = K - 1; k >= 0; --k) G.launch_bytes.push_back(vb * (nl_k[k] + nu_k[k]) + rowf * rows_k[k] + 24.0 * gx_b[k]);
-        G.gx_f = gx_f;
-        G.gx_b = gx_b;
-        G.rows_k = rows_k;
-        G.gx_r = gx_r;
-        G.gx_u = gx_u;
-        G.gx_l = gx_l;
-        G.nl_k = nl_k;
-        G.nu_k = nu_k;
-        G.vb = vb;
-    }
-    G.ncol = K;
-    G.nchunk = nch;
-    G.first.assign(KG, 0);
-    G.count.assign(KG, 0);
-    std::vector<int32_t> list;
-    for (int k = 0; k < KG; ++k) {
-        G.first[k] = (int64_t)list.size();
-        G.count[k] = (int64_t)bycol[k].size();
-        list.insert(list.end(), bycol[k].begin(), bycol[k].end());
-    }
-    if (vt != kVal64 && L.minv32.p) {
-        const std::vector<float> m32 = L.minv32.download();
-        std::vector<float> mc((size_t)nch * 9 * kChunk, 0.0f);
-#pragma omp parallel for schedule(static)
-        for (int64_t c = 0; c < nch; ++c)
-            for (int64_t lane = 0; lane < kChunk; ++lane) {
-                const int32_t rr = rowidx[c * kChunk + lane];
-                const int64_t g = rr >= 0 ? rr : ~rr;  // pad lanes: the chunk's first row (their x is not stored)
-                for (int ij = 0; ij < 9; ++ij) mc[(c * 9 + ij) * kChunk + lane] = m32[9 * g + ij];
-            }
-        G.minvc.upload(mc);
-    }
-    G.list.upload(list);
-    G.rowidx.upload(rowidx);
-    G.csub.upload(csub);
-    G.nsl.upload(nsl);
-    G.nsu.upload(nsu);
-    G.offl.upload(offl);
-    G.offu.upload(offu);
-    G.cb.upload(cb);
-    if (c16) G.col16.upload(gcol16);
-    else G.col.upload(gcol);
-    if (vt == kValH16) G.val16.upload(v16);
-    else if (vt == kValQ8) G.val8.upload(v8);
-    else if (vt == kVal32) G.val32.upload(v32);
-    else G.val64.upload(v64);
-    if (std::getenv("DDPCA_VERBOSE")) {
-        int64_t nb = 0, nr = 0, nf = 0;
-        for (int s = 0; s < nsub; ++s) nb += G.band_rows_sub[s], nr += G.ring_rows_sub[s], nf += G.far_rows_sub[s];
-        std::fprintf(stderr, "[ddpca] fine level: multicolour Gauss-Seidel, %d colours, %lld chunks, %lld slots%s\n", K,
-                     (long long)nch, (long long)nslot,
-                     band ? (", band " + std::to_string(nb) + " / ring " + std::to_string(nr) + " / far " + std::to_string(nf) + " rows").c_str() : "");
-    }
+    L.ppar.upload(T.ppar);
+    if (!T.uw) L.pw.upload(T.pw);
+    L.rslots.upload(T.rslots);
+    L.roff.upload(T.roff);
+    L.rcol.upload(T.rcol);
+    L.rwt.upload(T.rwt);
 }
 }  // namespace
 
 MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const mgpis_options_t& o, bool gen,
                          bool diag_only)
     : general(gen), device(dev), opt(o) {
+    // ---- validate
     select_device(device);
     nsub = (int)subs.size();
     if (nsub < 1) throw ApiError(DDPCA_EINVAL, "empty subdomain batch");
@@ -2095,472 +1509,66 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
     if (opt.smoother == 4 && opt.precond_fp32 == 0 && nlev > 1)
         throw ApiError(DDPCA_ESTATE, "colour SSOR needs a reduced-precision V-cycle copy (precond_fp32 >= 1)");
     const bool bj = opt.smoother >= 1;
-    // device numbering: perm[l][s][reference local node] = device local node.  Levels >= 1 with
-    // coordinates: lexicographic, or -- table mode, when the level's distinct rows compress --
-    // grouped by row type so chunks are type-homogeneous; their slots go in canonical order.
-    std::vector<std::vector<std::vector<int32_t>>> perm(nlev, std::vector<std::vector<int32_t>>(nsub));
-    std::vector<std::vector<std::vector<Key3>>> keys(nlev, std::vector<std::vector<Key3>>(nsub));
-    std::vector<char> grouped(nlev, 0);
-    for (int l = 0; l < nlev; ++l) {
-        bool geo = l > 0;
-        for (int s = 0; s < nsub; ++s) geo = geo && subs[s].coords != nullptr;
-        if (!geo) {
-            for (int s = 0; s < nsub; ++s) perm[l][s] = identity_order(subs[s].nnodes[l]);
-            continue;
-        }
-        std::vector<std::vector<int32_t>> types(nsub);
-        double tab_blocks = 0.0, blocks = 0.0;
-#pragma omp parallel for schedule(dynamic, 1) reduction(+ : tab_blocks, blocks)
-        for (int s = 0; s < nsub; ++s) {
-            const Bsr3& A = *subs[s].K[l];
-            keys[l][s] = quantised_keys(subs[s].coords, subs[s].nnodes[l]);
-            if (opt.table_mode == 0) continue;
-            int64_t nt = 0, tmax = 0;
-            for (int64_t r = 0; r < A.nb; ++r) tmax = std::max<int64_t>(tmax, A.ptr[r + 1] - A.ptr[r]);
-            if (tmax > kMaxRowBlocks) continue;  // long rows: no table for this subdomain
-            types[s] = row_types(A, subs[s].free_flags(l), keys[l][s], nt);
-            tab_blocks += (double)nt * (double)tmax;
-            blocks += (double)A.nnzb();
-        }
-        grouped[l] = opt.table_mode == 2 || (opt.table_mode == 1 && tab_blocks <= 0.2 * blocks);
-        for (int s = 0; s < nsub; ++s)
-            perm[l][s] = device_order(keys[l][s], grouped[l] && !types[s].empty() ? &types[s] : nullptr);
-    }
+    const MgpisTuning tune = mgpis_tuning();  // the create-time variables, read once per handle
+
+    // ---- number the nodes
+    MgpisNumbering num = mgpis_numbering(subs, opt.table_mode);
+
+    // ---- per level: plan, upload, drop the plan
     lev.resize(nlev);
     for (int l = 0; l < nlev; ++l) {
         LevelDev& L = lev[l];
-        L.noff.resize(nsub);
-        L.nloc.resize(nsub);
-        int64_t tot = 0;
-        for (int s = 0; s < nsub; ++s) {
-            L.noff[s] = tot;
-            L.nloc[s] = subs[s].nnodes[l];
-            tot += pad64(L.nloc[s]);
-        }
-        L.nn = tot;
-        L.nch = tot / kChunk;
-        std::vector<int32_t> slots(L.nch, 0), csub(L.nch, 0);
-        std::vector<int64_t> off(L.nch + 1, 0);
-        for (int s = 0; s < nsub; ++s) {
-            const Bsr3& A = *subs[s].K[l];
-            const auto& p = perm[l][s];
-            const int64_t c0 = L.noff[s] / kChunk;
-            for (int64_t c = c0; c < c0 + pad64(L.nloc[s]) / kChunk; ++c) csub[c] = s;
-            for (int64_t r = 0; r < L.nloc[s]; ++r) {
-                int32_t& sl = slots[c0 + p[r] / kChunk];
-                sl = std::max<int32_t>(sl, (int32_t)(A.ptr[r + 1] - A.ptr[r]));
-            }
-            L.nnzb += A.nnzb();
-            L.nnzb_sub.push_back(A.nnzb());
-        }
-        for (int64_t c = 0; c < L.nch; ++c) off[c + 1] = off[c] + slots[c];
-        L.nslots = off[L.nch];
-        std::vector<int32_t> col(L.nslots * kChunk, 0);
-        std::vector<double> val(L.nslots * kChunk * 9, 0.0);
-        std::vector<double> dinv(3 * L.nn, 0.0), minv(bj ? 9 * L.nn : 3 * L.nn, 0.0);
-        std::vector<uint8_t> mask(L.nn, 0);
-        for (int s = 0; s < nsub; ++s) {
-            const Bsr3& A = *subs[s].K[l];
-            const uint8_t* fr = subs[s].free_flags(l);  // reference order: level-l nodes are a prefix
-            const auto& p = perm[l][s];
-            const int64_t base = L.noff[s];
-            // padded rows of the subdomain: self column, zero values
-            for (int64_t r = L.nloc[s]; r < pad64(L.nloc[s]); ++r) {
-                const int64_t g = base + r, c = g / kChunk, lane = g % kChunk;
-                for (int64_t q = off[c]; q < off[c + 1]; ++q) col[q * kChunk + lane] = (int32_t)g;
-            }
-#pragma omp parallel for schedule(static)
-            for (int64_t r = 0; r < L.nloc[s]; ++r) {
-                const int64_t g = base + p[r], c = g / kChunk, lane = g % kChunk;
-                uint8_t m = 0;
-                for (int a = 0; a < 3; ++a) m |= fr[3 * r + a] ? (1 << a) : 0;
-                mask[g] = m;
-                // this row's blocks in canonical order (= increasing device column under the
-                // lexicographic numbering), else in increasing device column
-                const int64_t len = A.ptr[r + 1] - A.ptr[r];
-                thread_local std::vector<int64_t> ordv;  // rows of any length (LAGRANGE's condensed systems)
-                ordv.resize(len);
-                int64_t* ord = ordv.data();
-                if (!keys[l][s].empty()) {
-                    canonical_slots(A, r, keys[l][s], ord);
-                } else {
-                    for (int64_t t = 0; t < len; ++t) ord[t] = A.ptr[r] + t;
-                    std::sort(ord, ord + len, [&](int64_t u, int64_t v) { return p[A.col[u]] < p[A.col[v]]; });
-                }
-                double diag[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-                for (int64_t t = 0; t < len; ++t) {
-                    const int64_t k = ord[t], q = off[c] + t;
-                    const int64_t j = A.col[k];
-                    col[q * kChunk + lane] = (int32_t)(base + p[j]);
-                    for (int a = 0; a < 3; ++a)
-                        for (int b = 0; b < 3; ++b) {
-                            double v = A.val[9 * k + 3 * a + b];
-                            if (!fr[3 * r + a] || !fr[3 * j + b]) v = (j == r && a == b) ? 1.0 : 0.0;
-                            val[(q * 9 + 3 * a + b) * kChunk + lane] = v;
-                            if (j == r) diag[3 * a + b] = v;
-                        }
-                }
-                for (int64_t q = off[c] + len; q < off[c + 1]; ++q) col[q * kChunk + lane] = (int32_t)g;
-                for (int a = 0; a < 3; ++a) dinv[3 * g + a] = fr[3 * r + a] ? 1.0 / diag[4 * a] : 0.0;
-                if (bj) {
-                    double inv[9];
-                    if (!invert3(diag, inv)) for (int q = 0; q < 9; ++q) inv[q] = 0.0;
-                    for (int a = 0; a < 3; ++a)
-                        for (int b = 0; b < 3; ++b)
-                            minv[9 * g + 3 * a + b] = (fr[3 * r + a] && fr[3 * r + b]) ? inv[3 * a + b] : 0.0;
-                } else {
-                    for (int a = 0; a < 3; ++a) minv[3 * g + a] = dinv[3 * g + a];
-                }
-            }
-        }
-        L.slots.upload(slots);
-        L.csub.upload(csub);
-        L.off.upload(off);
-        L.col.upload(col);
         {
-            // relative 16-bit columns when every offset of the level fits (DDPCA_COL16=0: off)
-            static const bool want16 = !std::getenv("DDPCA_COL16") || std::atoi(std::getenv("DDPCA_COL16")) != 0;
-            bool fits = want16;
-            std::vector<int16_t> col16(want16 ? col.size() : 0);
-            for (int64_t c = 0; c < L.nch && fits; ++c)
-                for (int64_t q = off[c]; q < off[c + 1] && fits; ++q)
-                    for (int64_t lane = 0; lane < kChunk; ++lane) {
-                        const int64_t d = (int64_t)col[q * kChunk + lane] - (c * kChunk + lane);
-                        if (d < INT16_MIN || d > INT16_MAX) { fits = false; break; }
-                        col16[q * kChunk + lane] = (int16_t)d;
-                    }
-            if (fits) L.col16.upload(col16);
-        }
-        if (opt.table_mode != 0 && l >= 1) build_table(L, slots, off, val, opt.table_mode == 2 || grouped[l]);
-        if (std::getenv("DDPCA_VERBOSE"))
-            std::fprintf(stderr, "[ddpca] level %d: %lld nodes, %lld chunks, %lld slots, table %d (%lld types, %lld uniform chunks)\n",
-                         l, (long long)L.nn, (long long)L.nch, (long long)L.nslots, (int)L.tbl, (long long)L.ntypes,
-                         (long long)L.nuniform);
-        // fp64 values: the fine level (Krylov operator) and, without the fp32 preconditioner
-        // copy, every level; the fp32 copy serves the V-cycle on levels >= 1 (level 0 is the
-        // dense inverse).  Table-mode levels need neither.
-        const bool vc32 = opt.precond_fp32 != 0 && nlev > 1;
-        const int64_t nslot = L.nslots;
-        // every (slot, lane) of the V-cycle copy, in the Krylov operator's slot order
-        auto for_vc_slots = [&](auto&& put) {
-#pragma omp parallel for schedule(static)
-            for (int64_t q = 0; q < nslot; ++q)
-                for (int64_t lane = 0; lane < kChunk; ++lane) put(q, q, lane);
-        };
-        const int64_t vc_nslot = nslot;
-        if (!L.tbl && (l == nlev - 1 || !vc32)) {
-            // (every element is written below: no serial zero fill of the level's largest array)
-            std::unique_ptr<double[]> v64(new double[val.size()]);
-#pragma omp parallel for schedule(static)
-            for (int64_t q = 0; q < nslot; ++q)
-                for (int ij = 0; ij < 9; ++ij)
-                    for (int64_t lane = 0; lane < kChunk; ++lane)
-                        v64[q * 9 * kChunk + slot_elem<double>(ij, lane)] = val[(q * 9 + ij) * kChunk + lane];
-            L.val.upload(v64.get(), val.size());
-        }
-        // levels in block-exponent fp16: the finest h16_levels (DDPCA_H16_LEVELS, default 3: +2 % over 1 under block
-        // Jacobi, profiles/r01_sweep_h16.txt; with the multicolour fine level 3 over 2 +1.1 % at 8 subdomains,
-        // +0.4 % at 2, 1 over 2 -4 %, the same 18.0 PCG iterations, profiles/r04j/ab_h16.txt)
-        static const int h16_levels = std::getenv("DDPCA_H16_LEVELS") ? std::atoi(std::getenv("DDPCA_H16_LEVELS")) : 3;
-        // precond_fp32 = 3: the same levels in block-scaled int8 (the finest DDPCA_Q8_LEVELS of them, default all)
-        static const int q8_levels = std::getenv("DDPCA_Q8_LEVELS") ? std::atoi(std::getenv("DDPCA_Q8_LEVELS")) : 64;
-        const bool lowp = !L.tbl && vc32 && l >= 1 && l >= nlev - h16_levels && opt.precond_fp32 >= 2;
-        // (a level with a block whose scale leaves fp32's normal range -- entries beyond ~1e38 or
-        // below ~1e-36 -- keeps the block-exponent fp16 copy, whose exponent has no such limit)
-        bool q8_done = false;
-        if (lowp && opt.precond_fp32 >= 3 && l >= nlev - q8_levels) {
-            std::vector<uint8_t> v8((size_t)vc_nslot * 12 * kChunk, 0);
-            std::atomic<bool> ok{true};
-            for_vc_slots([&](int64_t q, int64_t dst, int64_t lane) {
-                double blk[9];
-                uint8_t rec[12];
-                for (int ij = 0; ij < 9; ++ij) blk[ij] = val[(q * 9 + ij) * kChunk + lane];
-                if (!to_q8_block(blk, rec)) ok = false;
-                for (int k = 0; k < 12; ++k) v8[dst * 12 * kChunk + q8_pos(k, lane)] = rec[k];
-            });
-            if (ok) {
-                L.val8.upload(v8);
-                q8_done = true;
-            } else if (std::getenv("DDPCA_VERBOSE")) {
-                std::fprintf(stderr, "[ddpca] level %d: int8 scale out of range, block-exponent fp16 copy instead\n", l);
+            LevelPlan P = plan_level(subs, num, l, bj, opt.table_mode, tune);
+            upload_index(L, P);
+            std::vector<int16_t>().swap(P.col16);  // (a quarter of the index arrays: not held while the values are packed)
+            // fp64 values: the fine level (Krylov operator) and, without the reduced-precision
+            // preconditioner copy, every level; the copy serves the V-cycle on levels >= 1 (level 0
+            // is the dense inverse).  Table-mode levels need neither.
+            const bool copy = !P.tbl && vc32() && l >= 1;
+            if (!P.tbl && (l == nlev - 1 || !vc32())) upload_values(pack_values(P, kVal64), L.val, L.val32, L.val16, L.val8);
+            if (copy)
+                upload_values(level_copy(P, level_copy_type(opt.precond_fp32, l, nlev, tune), l, tune), L.val, L.val32, L.val16,
+                              L.val8);
+            L.dinv.upload(P.dinv);
+            L.minv.upload(P.minv);
+            // reduced-precision levels smooth with an fp32 inverse
+            std::vector<float> m32;
+            if (copy) {
+                m32 = smoother_inverse_fp32(P.minv, bj, !general);
+                L.minv32.upload(m32);
             }
-        }
-        if (!q8_done && lowp) {
-            // block-exponent fp16 copy of the fine level for the smoother and the V-cycle
-            // residual (symmetric: a block and its transpose round alike); coarser levels fp32
-            std::vector<uint16_t> v16((size_t)vc_nslot * 10 * kChunk, 0);  // zero blocks: e = 0, values 0
-            for_vc_slots([&](int64_t q, int64_t dst, int64_t lane) {
-                double blk[9];
-                uint16_t rec[10];
-                for (int ij = 0; ij < 9; ++ij) blk[ij] = val[(q * 9 + ij) * kChunk + lane];
-                to_h16_block(blk, rec);
-                for (int k = 0; k < 10; ++k) v16[dst * 10 * kChunk + 128 * (k / 2) + 2 * lane + k % 2] = rec[k];
-            });
-            L.val16.upload(v16);
-        } else if (!q8_done && !L.tbl && vc32 && l >= 1) {
-            std::vector<float> v32((size_t)vc_nslot * 9 * kChunk, 0.0f);
-            for_vc_slots([&](int64_t q, int64_t dst, int64_t lane) {
-                for (int ij = 0; ij < 9; ++ij)
-                    v32[dst * 9 * kChunk + slot_elem<float>(ij, lane)] = (float)val[(q * 9 + ij) * kChunk + lane];
-            });
-            L.val32.upload(v32);
-        }
-        L.dinv.upload(dinv);
-        L.minv.upload(minv);
-        if (!L.tbl && vc32 && l >= 1) {
-            // reduced-precision levels smooth with an fp32 inverse, symmetrised before rounding
-            // so the V-cycle stays exactly symmetric (block Jacobi: M_ab = M_ba)
-            std::vector<float> m32(minv.size());
-            const int w = bj ? 9 : 3;
-#pragma omp parallel for schedule(static)
-            for (int64_t g = 0; g < L.nn; ++g) {
-                const double* m = minv.data() + w * g;
-                for (int k = 0; k < w; ++k)
-                    m32[w * g + k] = bj && !general ? (float)(0.5 * (m[k] + m[3 * (k % 3) + k / 3])) : (float)m[k];
+            if (l == nlev - 1 && nlev > 1 && opt.smoother >= 3) {
+                // band mode (locally refined fine level): elsewhere the stencils are level
+                // l - 1's, which the V-cycle smooths next (colour SSOR sweeps every row)
+                std::vector<uint8_t> band;
+                if (opt.smoother == 3) band = colour_band(subs, num, l, P, tune);
+                upload_colours(gs, plan_colours(P, vc_type(l), copy ? &m32 : nullptr, band.empty() ? nullptr : &band, tune));
             }
-            L.minv32.upload(m32);
+            L.mask.upload(P.mask);
         }
-        if (l == nlev - 1 && nlev > 1 && opt.smoother >= 3) {
-            const int vt = vc_type(l);  // (the level's value buffers are uploaded by now)
-            // band mode (locally refined fine level): sweep only the nodes this level
-            // adds to level l - 1 (reference positions past nnodes[l - 1]) and their neighbours --
-            // elsewhere the stencils are level l - 1's, which the V-cycle smooths next -- when that
-            // is at most 60 % of the rows; DDPCA_GS_BAND=0 sweeps every row
-            std::vector<uint8_t> bandv;
-            const char* be = std::getenv("DDPCA_GS_BAND");
-            if (!(be && be[0] == '0') && opt.smoother == 3) {  // (colour SSOR sweeps every row)
-                bandv.assign(L.nn, 0);
-                int64_t nreal = 0, nband = 0;
-                for (int s = 0; s < nsub; ++s) {
-                    nreal += L.nloc[s];
-                    for (int64_t ref = subs[s].nnodes[l - 1]; ref < subs[s].nnodes[l]; ++ref)
-                        bandv[L.noff[s] + perm[l][s][ref]] = 2;  // new node
-                }
-                for (int64_t g = 0; g < L.nn; ++g) {
-                    if (bandv[g] != 2) continue;
-                    const int64_t c = g / kChunk, lane = g % kChunk;
-                    for (int64_t q = off[c]; q < off[c + 1]; ++q) {
-                        bool nz = false;
-                        for (int ij = 0; ij < 9 && !nz; ++ij) nz = val[(q * 9 + ij) * kChunk + lane] != 0.0;
-                        const int64_t j = col[q * kChunk + lane];
-                        if (nz && bandv[j] == 0) bandv[j] = 1;
-                    }
-                }
-                for (uint8_t f : bandv) nband += f != 0;
-                if (nband == 0 || nband > (nreal * 3) / 5) bandv.clear();
-            }
-            build_gs(gs, L, nsub, off, col, val, vt, bandv.empty() ? nullptr : &bandv);
-        }
-        L.mask.upload(mask);
         for (auto* v : {&L.x, &L.t, &L.b, &L.r, &L.d}) {
             v->alloc(3 * L.nn);
             v->zero(stream);
         }
-        if (l > 0) {
-            const LevelDev& C = lev[l - 1];
-            std::vector<int32_t> ppar(8 * L.nn, -1);
-            std::vector<double> pw(8 * L.nn, 0.0);
-            bool uw = true;  // every weight == 1 / the node's parent count
-            std::vector<std::vector<std::pair<int32_t, double>>> kids(C.nn);
-            struct ExtraEnt {
-                int32_t f, c;
-                double b[9];
-            };
-            std::deque<ExtraEnt> extra;  // scalar parents past the eighth, as blocks
-            L.tent_sub.assign(nsub, 0);
-            L.tblk_sub.assign(nsub, 0);
-            for (int s = 0; s < nsub; ++s) {
-                const Stencil& st = *subs[s].S[l - 1];
-                const auto& pf = perm[l][s];
-                const auto& pc = perm[l - 1][s];
-                const int64_t nc = C.nloc[s];
-                if (st.nf != L.nloc[s] || st.nc != nc) throw ApiError(DDPCA_EINVAL, "stencil shape");
-                L.tblk_sub[s] = (int64_t)st.bent.size();
-                L.tent_sub[s] = (int64_t)st.col.size() - L.tblk_sub[s];
-                // block entries (weight 0 in the scalar stencil) run in k_prolong_rot / k_restrict_rot
-                // only: they take no parent slot (a node may have any number of them)
-                std::vector<uint8_t> isblk(st.col.size(), 0);
-                for (int64_t e : st.bent) isblk[e] = 1;
-                if (!st.bent.empty()) uw = false;
-                for (int64_t i = 0; i < L.nloc[s]; ++i) {
-                    int64_t np = 0;
-                    for (int64_t e = st.ptr[i]; e < st.ptr[i + 1]; ++e) np += !isblk[e];
-                    const int64_t gf = L.noff[s] + pf[i];
-                    if (i < nc) {
-                        if (np != 1 || st.col[st.ptr[i]] != i || st.w[st.ptr[i]] != 1.0)
-                            throw ApiError(DDPCA_EINVAL, "stencil is not identity on coarse nodes");
-                        const int64_t gc = C.noff[s] + pc[i];
-                        ppar[gf] = (int32_t)gc;
-                        pw[gf] = 1.0;
-                        kids[gc].insert(kids[gc].begin(), {(int32_t)gf, 1.0});
-                        continue;
-                    }
-                    // parents past the eighth (LAGRANGE's condensed transfers) run as w*I blocks
-                    if (np > 8) uw = false;
-                    int64_t k = 0;
-                    for (int64_t e = st.ptr[i]; e < st.ptr[i + 1]; ++e) {
-                        if (isblk[e]) continue;
-                        if (k == 8) {
-                            extra.push_back({(int32_t)gf, (int32_t)(C.noff[s] + pc[st.col[e]]), {}});
-                            for (int q = 0; q < 9; ++q) extra.back().b[q] = q % 4 == 0 ? st.w[e] : 0.0;
-                            continue;
-                        }
-                        if (st.w[e] != 1.0 / (double)np) uw = false;
-                        const int64_t gc = C.noff[s] + pc[st.col[e]];
-                        ppar[k * L.nn + gf] = (int32_t)gc;
-                        pw[k * L.nn + gf] = st.w[e];
-                        kids[gc].push_back({(int32_t)gf, st.w[e]});
-                        ++k;
-                    }
-                }
-            }
-            // restriction children in SELL-64 over the coarse chunks; padding slots carry weight 0
-            // on the node's own first child (or fine node 0 for padding nodes)
-            std::vector<int32_t> rsl(C.nch, 0);
-            std::vector<int64_t> rof(C.nch + 1, 0);
-            for (int64_t c = 0; c < C.nch; ++c) {
-                size_t mx = 0;
-                for (int64_t j = c * kChunk; j < (c + 1) * kChunk; ++j) mx = std::max(mx, kids[j].size());
-                rsl[c] = (int32_t)mx;
-                rof[c + 1] = rof[c] + (int64_t)mx;
-            }
-            std::vector<int32_t> rcol(std::max<int64_t>(rof[C.nch] * kChunk, 1), 0);
-            std::vector<double> rwt(std::max<int64_t>(rof[C.nch] * kChunk, 1), 0.0);
-            for (int64_t j = 0; j < C.nn; ++j) {
-                const int64_t c = j / kChunk, lane = j % kChunk;
-                for (int64_t k = 0; k < rsl[c]; ++k) {
-                    const int64_t q = (rof[c] + k) * kChunk + lane;
-                    const bool real = k < (int64_t)kids[j].size();
-                    rcol[q] = real ? kids[j][k].first : (kids[j].empty() ? 0 : kids[j][0].first);
-                    rwt[q] = real ? kids[j][k].second : 0.0;
-                }
-            }
-            // block entries: (fine node, coarse node, 3x3) in batch-global indices, as CSR by
-            // fine node (prolongation) and by coarse node (restriction)
-            struct RotEnt {
-                int32_t f, c;
-                const double* b;
-            };
-            std::vector<RotEnt> ents;
-            for (int s = 0; s < nsub; ++s) {
-                const Stencil& st = *subs[s].S[l - 1];
-                if (st.bent.empty()) continue;
-                const auto& pf = perm[l][s];
-                const auto& pc = perm[l - 1][s];
-                int64_t i = 0;
-                for (size_t q = 0; q < st.bent.size(); ++q) {
-                    const int64_t e = st.bent[q];
-                    while (st.ptr[i + 1] <= e) ++i;
-                    if (st.w[e] != 0.0) throw ApiError(DDPCA_EINVAL, "block transfer entry with a scalar weight");
-                    ents.push_back({(int32_t)(L.noff[s] + pf[i]), (int32_t)(C.noff[s] + pc[st.col[e]]), &st.bval[9 * q]});
-                }
-            }
-            for (const ExtraEnt& x : extra) ents.push_back({x.f, x.c, x.b});
-            if (!ents.empty()) {
-                auto upload_csr = [&](bool by_fine, int64_t& nr, DevBuf<int32_t>& row, DevBuf<int64_t>& ptr_,
-                                      DevBuf<int32_t>& other, DevBuf<double>& blk) {
-                    std::stable_sort(ents.begin(), ents.end(), [by_fine](const RotEnt& a, const RotEnt& b) {
-                        return by_fine ? a.f < b.f : a.c < b.c;
-                    });
-                    std::vector<int32_t> r, o;
-                    std::vector<int64_t> pt{0};
-                    std::vector<double> bv;
-                    for (size_t q = 0; q < ents.size(); ++q) {
-                        const int32_t key = by_fine ? ents[q].f : ents[q].c;
-                        if (r.empty() || r.back() != key) {
-                            if (!r.empty()) pt.push_back((int64_t)q);
-                            r.push_back(key);
-                        }
-                        o.push_back(by_fine ? ents[q].c : ents[q].f);
-                        bv.insert(bv.end(), ents[q].b, ents[q].b + 9);
-                    }
-                    pt.push_back((int64_t)ents.size());
-                    nr = (int64_t)r.size();
-                    row.upload(r);
-                    ptr_.upload(pt);
-                    other.upload(o);
-                    blk.upload(bv);
-                };
-                upload_csr(true, L.nrot, L.rot_row, L.rot_ptr, L.rot_par, L.rot_blk);
-                upload_csr(false, L.nrotc, L.rotc_row, L.rotc_ptr, L.rotc_kid, L.rotc_blk);
-            }
-            // (read per handle: the general-mesh tests and bench line switch it off in-process)
-            const bool want_lat = !std::getenv("DDPCA_LATTICE") || std::atoi(std::getenv("DDPCA_LATTICE")) != 0;
-            if (want_lat && uw && ents.empty() && lattice_transfer(L, C, ppar, kids)) {
-                if (std::getenv("DDPCA_VERBOSE")) std::fprintf(stderr, "[ddpca] level %d: lattice transfers\n", l);
-                continue;
-            }
-            if (std::getenv("DDPCA_VERBOSE"))
-                std::fprintf(stderr, "[ddpca] level %d: explicit transfer lists (uniform averaging %d, block entries %zu)\n", l,
-                             (int)uw, ents.size());
-            L.ppar.upload(ppar);
-            L.uw = uw;  // prolongation weights from the parent count (restriction keeps rwt)
-            if (!uw) L.pw.upload(pw);
-            L.rslots.upload(rsl);
-            L.roff.upload(rof);
-            L.rcol.upload(rcol);
-            L.rwt.upload(rwt);
-        }
+        if (l > 0) upload_transfer(L, plan_transfer(subs, num, l, L, lev[l - 1], tune));
     }
-    fine_perm = perm[nlev - 1];
-    level_perm = perm;
-    // exact coarse solve: dense inverse of each subdomain's masked operator on level clev, in
-    // that level's device order.  clev: the option, or the highest level below the fine one
-    // whose inverses of all members fit in 256 MB (a few-subdomain batch trades the coarse
-    // levels' latency-bound launches for one GEMV over a larger dense inverse)
-    {
-        clev = 0;
-        if (opt.coarse_level >= 0) clev = std::min(opt.coarse_level, nlev - 1);
-        else
-            for (int l = nlev - 2; l >= 1; --l) {
-                double bytes = 0.0;
-                int64_t nmax = 0;
-                for (int s = 0; s < nsub; ++s) {
-                    const double n = 3.0 * (double)subs[s].nnodes[l];
-                    bytes += 8.0 * n * n;
-                    nmax = std::max<int64_t>(nmax, 3 * subs[s].nnodes[l]);
-                }
-                if (bytes <= 256.0 * 1024 * 1024 && nmax <= 12288) { clev = l; break; }
-            }
-        if (nlev > 1 && clev == nlev - 1) clev = nlev - 2;
-        int64_t n0max = 0;
-        for (int s = 0; s < nsub; ++s) n0max = std::max<int64_t>(n0max, 3 * subs[s].nnodes[clev]);
-        // a one-level handle too large for a dense inverse serves the diagonal-preconditioned
-        // drivers only (precSwit 0; the V-cycle then reports DDPCA_ESTATE)
-        no_coarse = diag_only || (nlev == 1 && n0max > 12288);
-    }
+    level_perm = std::move(num.perm);
+    fine_perm = level_perm[nlev - 1];
+
+    // ---- exact coarse solve: dense inverse of each subdomain's masked operator on level clev, in
+    // that level's device order.  A one-level handle too large for a dense inverse serves the
+    // diagonal-preconditioned drivers only (precSwit 0; the V-cycle then reports DDPCA_ESTATE)
+    int64_t n0max = 0;
+    clev = choose_coarse_level(subs, opt.coarse_level, &n0max);
+    no_coarse = diag_only || (nlev == 1 && n0max > 12288);
     if (!no_coarse) {
         std::vector<double> packed;
         std::vector<int64_t> ao(nsub), no(nsub), nz(nsub), ldv(nsub);
         for (int s = 0; s < nsub; ++s) {
-            const Bsr3& A = *subs[s].K[clev];
-            const uint8_t* fr = subs[s].free_flags(clev);
-            const auto& p = perm[clev][s];
-            const int64_t nc = subs[s].nnodes[clev], n0 = 3 * nc;
-            std::vector<double> D(n0 * n0, 0.0);
-            // a constrained dof's decoupled row and column (zeroed again after the inverse) carry 1,
-            // or in the general path the largest free diagonal entry, so that its pivot does not
-            // read as near-singular against stiffness-scaled ones (inv_general_lu_device's test)
-            double cdiag = 1.0;
-            if (general) {
-                cdiag = 0.0;
-                for (int64_t r = 0; r < nc; ++r)
-                    for (int64_t k = A.ptr[r]; k < A.ptr[r + 1]; ++k)
-                        if (A.col[k] == r)
-                            for (int a = 0; a < 3; ++a)
-                                if (fr[3 * r + a]) cdiag = std::max(cdiag, std::abs(A.val[9 * k + 4 * a]));
-                if (!(cdiag > 0.0)) cdiag = 1.0;
-            }
-            for (int64_t r = 0; r < nc; ++r)
-                for (int64_t k = A.ptr[r]; k < A.ptr[r + 1]; ++k) {
-                    const int64_t j = A.col[k];
-                    for (int a = 0; a < 3; ++a)
-                        for (int b = 0; b < 3; ++b) {
-                            double v = A.val[9 * k + 3 * a + b];
-                            if (!fr[3 * r + a] || !fr[3 * j + b]) v = (j == r && a == b) ? cdiag : 0.0;
-                            D[(3 * p[r] + a) * n0 + 3 * p[j] + b] = v;
-                        }
-                }
+            const auto& p = level_perm[clev][s];
+            const int64_t n0 = 3 * subs[s].nnodes[clev];
+            std::vector<double> D = coarse_dense(subs[s], clev, p, general);
             if (general) {
                 // LU inverse when the LU is clearly regular, else the SVD pseudo-inverse
                 double resid = INFINITY;
@@ -2568,29 +1576,17 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
                 int64_t dropped = 0;
                 if (!lu) pinv_general_device(D, n0, stream, &dropped);
                 coarse_inverse.push_back({lu ? 1 : 2, resid, dropped});
-                if (std::getenv("DDPCA_VERBOSE"))
+                if (tune.verbose)
                     std::fprintf(stderr, "[ddpca] coarse inverse: %s, %ld rows, LU residual %.3g, %ld singular values dropped\n",
                                  lu ? "LU" : "SVD pseudo-inverse", (long)n0, resid, (long)dropped);
             } else {
                 invert_spd_device(D, n0, stream);
                 coarse_inverse.push_back({0, 0.0, 0});
             }
-            for (int64_t r = 0; r < nc; ++r)
-                for (int a = 0; a < 3; ++a) {
-                    if (fr[3 * r + a]) continue;
-                    const int64_t d = 3 * p[r] + a;
-                    for (int64_t e = 0; e < n0; ++e) D[d * n0 + e] = D[e * n0 + d] = 0.0;
-                }
             ao[s] = (int64_t)packed.size();
             no[s] = lev[clev].noff[s];
             nz[s] = n0;
-            const int64_t ld = (n0 + 3) / 4 * 4;  // rows padded for 16-B loads (k_coarse)
-            if (ld > 3 * pad64(lev[clev].nloc[s])) throw ApiError(DDPCA_ESTATE, "coarse row padding beyond the member");
-            ldv[s] = ld;
-            for (int64_t r = 0; r < n0; ++r) {
-                packed.insert(packed.end(), D.begin() + r * n0, D.begin() + (r + 1) * n0);
-                packed.insert(packed.end(), ld - n0, 0.0);
-            }
+            ldv[s] = coarse_pack(D, subs[s], clev, p, pad64(lev[clev].nloc[s]), packed);
         }
         if (vc32()) {
             // reduced-precision preconditioner storage: the (exactly symmetric) dense inverses in
@@ -2603,9 +1599,11 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
         c_noff.upload(no);
         c_n.upload(nz);
         c_ld.upload(ldv);
-        if (std::getenv("DDPCA_VERBOSE"))
+        if (tune.verbose)
             std::fprintf(stderr, "[ddpca] exact coarse solve on level %d (%zu doubles of dense inverses)\n", clev, packed.size());
     }
+
+    // ---- work buffers
     // condensed <-> nodal map of the fine level
     const LevelDev& F = lev.back();
     nfree.resize(nsub);
@@ -2613,8 +1611,7 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
     free_dof.resize(nsub);
     std::vector<int64_t> cb(nsub + 1, 0);
     for (int s = 0; s < nsub; ++s) {
-        for (int64_t d = 0; d < 3 * F.nloc[s]; ++d)
-            if (subs[s].dof_free[d]) free_dof_host[s].push_back((int32_t)fine_dof(s, d));
+        free_dof_host[s] = free_dof_map(subs[s], fine_perm[s], F.noff[s]);
         nfree[s] = (int64_t)free_dof_host[s].size();
         free_dof[s].upload(free_dof_host[s]);
         cb[s] = F.noff[s] / kChunk;
@@ -2645,83 +1642,43 @@ MgpisDevice::MgpisDevice(int dev, const std::vector<SubdomainOps>& subs, const m
     if (gs_fine() && opt.precond_fp32 == 4 && !gs.band && lev.back().lat && lev.back().nrot == 0) {
         gs.x4.alloc(4 * lev.back().nn);
         gs.x4.zero(stream);
-        // the residual the restriction reads, in fp32 too (DDPCA_GS_R32=0: fp64, A/B)
-        const char* er = std::getenv("DDPCA_GS_R32");
-        if (!(er && er[0] == '0')) {
+        if (tune.gs_r32) {  // the residual the restriction reads, in fp32 too
             gs.r4.alloc(4 * lev.back().nn);
             gs.r4.zero(stream);
         }
-        // the per-launch byte model on the 16-B iterate: gathers 16 instead of 24 B per distinct
-        // node, the forward sweep writes 16 B per row, the backward sweep 16 + 24 (colour SSOR
-        // builds its own model below)
-        const int K = opt.smoother == 3 ? gs.ncol : 0;
-        for (int k = 0; k < K; ++k) {
-            gs.launch_bytes[k] -= 8.0 * gs.gx_f[k] + 8.0 * gs.rows_k[k];
-            gs.launch_bytes[2 * K - k] += -8.0 * gs.gx_b[k] + 16.0 * gs.rows_k[k];
-        }
-        if (K) gs.launch_bytes[K] -= 8.0 * gs.gx_r;
-        if (gs.r4.p)
-            for (int k = 0; k < K; ++k) gs.launch_bytes[K] -= 8.0 * gs.rows_k[k];  // r written in 16 B
     }
-    // fp32 iterate copies of the block-Jacobi levels (precond_fp32 = 4, block-Jacobi smoothing;
-    // DDPCA_BJ_X4=0 keeps them fp64, A/B): every level the V-cycle smooths by block Jacobi whose
+    // fp32 iterate copies of the block-Jacobi levels (precond_fp32 = 4, block-Jacobi smoothing):
+    // every level the V-cycle smooths by block Jacobi whose
     // copy has 16-bit columns and streamed values (rotation block entries into it included) -- its
     // sweeps and residual gather one 16-B load per neighbour, only the level's last sweep writes
     // fp64.  Alternating in one call (profiles/r06n): the N = 8 rank 9.52 / 9.55 -> 9.00 / 9.00 ms
     // per ADMM iteration, the headline 19.73 / 19.74 -> 20.05 / 20.06 ADMM it/s, PCG iterations equal
-    {
-        const char* eb = std::getenv("DDPCA_BJ_X4");
-        const bool on = !(eb && eb[0] == '0');
-        if (on && opt.precond_fp32 == 4 && (opt.smoother == 1 || opt.smoother >= 3))
-            for (int l = clev + 1; l < (int)lev.size(); ++l) {
-                LevelDev& L = lev[l];
-                if ((gs_fine() && l == (int)lev.size() - 1) || !L.col16.p || L.tbl) continue;
-                L.x4a.alloc(4 * L.nn);
-                L.x4b.alloc(4 * L.nn);
-                L.x4a.zero(stream);
-                L.x4b.zero(stream);
-            }
-    }
+    if (tune.bj_x4 && opt.precond_fp32 == 4 && (opt.smoother == 1 || opt.smoother >= 3))
+        for (int l = clev + 1; l < (int)lev.size(); ++l) {
+            LevelDev& L = lev[l];
+            if ((gs_fine() && l == (int)lev.size() - 1) || !L.col16.p || L.tbl) continue;
+            L.x4a.alloc(4 * L.nn);
+            L.x4b.alloc(4 * L.nn);
+            L.x4a.zero(stream);
+            L.x4b.zero(stream);
+        }
     if (gs_fine() && opt.smoother == 4) {
         gs.w.alloc(3 * lev.back().nn);
         gs.w.zero(stream);
-        // the per-launch byte model in k_gs_ssor's launch order: forward colours 0..K-1 (L), backward
-        // K-1..0 (U), the residual (L, every chunk), forward 0..K-1 (L + U), backward K-1..0 (U); per
-        // row b, the fp32 inverse, w and x as each phase moves them, x gathered once per distinct node
-        const int K = gs.ncol;
-        const double xb = gs.x4.p ? 16.0 : 24.0, rb = gs.r4.p ? 16.0 : 24.0, m = 36.0, ix = 4.0;
-        std::vector<double> lb;
-        for (int k = 0; k < K; ++k) lb.push_back(gs.vb * gs.nl_k[k] + gs.rows_k[k] * (24 + m + xb + 24 + ix) + xb * gs.gx_f[k]);
-        for (int k = K - 1; k >= 0; --k) lb.push_back(gs.vb * gs.nu_k[k] + gs.rows_k[k] * (48 + m + xb + ix) + xb * gs.gx_u[k]);
-        double res = xb * gs.gx_l;
-        for (int k = 0; k < K; ++k) res += gs.vb * gs.nl_k[k] + gs.rows_k[k] * (24 + rb + ix);
-        lb.push_back(res);
-        for (int k = 0; k < K; ++k)
-            lb.push_back(gs.vb * (gs.nl_k[k] + gs.nu_k[k]) + gs.rows_k[k] * (24 + m + xb + 24 + ix) + xb * gs.gx_b[k]);
-        for (int k = K - 1; k >= 0; --k)
-            lb.push_back(gs.vb * gs.nu_k[k] + gs.rows_k[k] * (48 + m + 24 + (gs.x4.p ? xb : 0.0) + ix) + xb * gs.gx_u[k]);
-        gs.launch_bytes = lb;
     }
+    // the colour plan's byte model is smoother 3's on fp64 iterates
+    if (gs_fine() && (gs.x4.p || opt.smoother == 4)) colour_byte_model(gs, opt.smoother, gs.x4.p != nullptr, gs.r4.p != nullptr);
     sc.alloc(nsub);
     DDPCA_HIP(hipHostMalloc(reinterpret_cast<void**>(&sc_host), nsub * sizeof(PcgScal)));
     std::memset(sc_host, 0, nsub * sizeof(PcgScal));
     mirror.alloc(nsub);
     DDPCA_HIP(hipEventCreate(&ev_k0));
     DDPCA_HIP(hipEventCreate(&ev_k1));
-    // smoother coefficients from the spectrum of M K on each smoothed level and subdomain
+
+    // ---- smoother coefficients from the spectrum of M K on each smoothed level and subdomain
     for (int l = 1; l < nlev; ++l) {
         estimate_lmax(l);
-        std::vector<double> coef(2 * (opt.nu + 1) * nsub, 0.0);
-        for (int k = 0; k <= opt.nu; ++k)
-            for (int s = 0; s < nsub; ++s) {
-                double c1 = 0.0, c2;
-                if (opt.smoother == 2) cheb_coef(lev[l].lmax[s], k, c1, c2);
-                else c2 = opt.omega > 0.0 ? opt.omega
-                          : (opt.omega < 0.0 ? -opt.omega : 4.0 / 3.0) / lev[l].lmax[s];
-                coef[2 * (k * nsub + s)] = c1;
-                coef[2 * (k * nsub + s) + 1] = c2;
-            }
-        lev[l].coef.upload(coef);
+        lev[l].coef.upload(smoother_coefs(lev[l].lmax, opt.nu, opt.smoother, opt.omega));
     }
     DDPCA_HIP(hipStreamSynchronize(stream));
 }

@@ -38,12 +38,10 @@
 
 #include "../../include/ddpca_amd.h"
 #include "device_common.hpp"
+#include "mgpis_plan.hpp"
 #include "sparse.hpp"
 
 namespace ddpca {
-
-// Storage type of streamed operator values (arithmetic is fp64 throughout).
-enum ValType { kVal64 = 0, kVal32 = 1, kValH16 = 2, kValQ8 = 3 };  // H16: block-exponent fp16, Q8: block-scaled int8
 
 // Per-subdomain scalar block of the PCG recurrence (device memory, read by every kernel).
 struct PcgScal {
@@ -59,24 +57,9 @@ struct PcgScal {
     int fail;         // 1: NaN/Inf or non-positive curvature
 };
 
-// Operators of one subdomain, in the host (MULTIGRID restatement) layout.
-struct SubdomainOps {
-    std::vector<int64_t> nnodes;           // nodes of level <= l
-    std::vector<const Bsr3*> K;            // unconstrained Galerkin operator per level
-    const uint8_t* dof_free = nullptr;     // 3 * nnodes.back() flags (consFlag)
-    // optional per-level flags (3 * nnodes[l] each) where a dof's status differs between levels
-    // (LATIN's DOUBLE_M: a coarse contact node its finer level does not carry is a masked copy
-    // there); empty = the fine flags' prefix on every level (consOper, MULTIGRID.h:1186-1243)
-    std::vector<const uint8_t*> dof_free_lev;
-    const uint8_t* free_flags(int l) const { return dof_free_lev.empty() ? dof_free : dof_free_lev[l]; }
-    std::vector<const Stencil*> S;         // scalar prolongation stencils, nlev - 1
-    const double* coords = nullptr;        // optional 3 * nnodes.back() node coordinates: when
-                                           // given, levels >= 1 are renumbered on the device
-};
-
-struct LevelDev {
-    int64_t nn = 0, nch = 0, nslots = 0, nnzb = 0;  // batch totals (nn, nch padded)
-    std::vector<int64_t> noff, nloc, nnzb_sub;      // per subdomain: first node, real nodes, blocks
+// One level on the device: the scalar parts of its plans (LevelShape, TransferShape: mgpis_plan.hpp)
+// and one buffer per plan vector.
+struct LevelDev : LevelShape, TransferShape {
     DevBuf<int32_t> slots, col, csub;               // csub: chunk -> subdomain
     DevBuf<int16_t> col16;  // col - row node when every offset of the level fits 16 bits (else empty)
     DevBuf<int64_t> off;
@@ -85,13 +68,7 @@ struct LevelDev {
     DevBuf<float> val32;   // V-cycle operator rounded once to fp32 (opt.precond_fp32), levels >= 1
     DevBuf<uint16_t> val16;  // fine level's V-cycle copy in block-exponent fp16 (opt.precond_fp32 = 2)
     DevBuf<uint8_t> val8;    // ... in block-scaled int8 (opt.precond_fp32 = 3)
-    // table mode: rows whose block values (in device slot order, masks applied) are bit-identical
-    // share one table row; the kernel streams only column indices and a row type, the values
-    // come from the cache-resident table (structured meshes: ~30x fewer distinct rows than rows)
-    bool tbl = false;
-    int64_t tstride = 0;     // doubles per table row (max row length * 9)
-    int64_t ntypes = 0;
-    int64_t nuniform = 0;    // chunks whose rows all share one type
+    // table mode (LevelShape::tbl): the row types and the table
     DevBuf<int32_t> rtype;   // per node row
     DevBuf<int32_t> ctype;   // per chunk: the common type, -1 = mixed
     DevBuf<double> tab;
@@ -102,32 +79,14 @@ struct LevelDev {
     DevBuf<uint8_t> mask;  // bit a set = dof 3i+a free
     DevBuf<double> coef;   // [(sweep * nsub + sub) * 2 + {0,1}]: Chebyshev (c1, c2) / Jacobi (-, omega)
     std::vector<double> lmax;  // per subdomain, lambda_max(M K)
-    // transfer from level l-1 (batch-global indices)
-    std::vector<int64_t> tent_sub, tblk_sub;  // per subdomain: scalar stencil entries, 3x3 block entries
-    DevBuf<int32_t> ppar;  // 8 x nn, slot-major, -1 = unused
-    DevBuf<double> pw;     // weights (empty when uw)
-    bool uw = false;       // uniform averaging: prolongation weight = 1 / parent count (nested
-                           // refinement), computed in k_prolong instead of read
-    // restriction: SELL-64 over the coarse nodes of level l-1 (chunk = 64 coarse nodes, lane =
-    // node, slot k = k-th child: own fine copy first, padding = weight 0)
-    DevBuf<int32_t> rslots;  // per coarse chunk
-    DevBuf<int64_t> roff;    // per coarse chunk + 1
-    DevBuf<int32_t> rcol;    // fine node
-    DevBuf<double> rwt;
-    // lattice transfers (uniform averaging on a lexicographically numbered box lattice, detected
-    // at create, off with DDPCA_LATTICE=0): a fine node's parents are p0 + subset sums of three
-    // coarse strides, a coarse node's children its fine copy f0 + sum d_k t_k (d in {-1,0,1}^3)
-    // with weight 2^-|d|; the kernels compute the indices instead of streaming ppar / rcol / rwt
-    bool lat = false;
-    DevBuf<uint32_t> ppk;   // per fine node: p0 | (stride-subset code << 29)
-    DevBuf<int32_t> pstr;   // per subdomain: 3 coarse strides
-    DevBuf<uint32_t> rmsk;  // per coarse node: 27-bit mask of the children present, bit (d0+1) + 3(d1+1) + 9(d2+1)
-    DevBuf<int32_t> rf0;    // per coarse node: its fine copy
-    DevBuf<int32_t> rstr;   // per subdomain: 3 fine strides
-    // block transfer entries (nodal rotations, MULTIGRID.h:1141-1181): P = S (x) I3 + sum of
-    // 3x3 blocks, as CSR over the fine nodes that own one (prolongation) and over the coarse
-    // nodes that receive one (restriction, B^T); nrot = 0 on plain S (x) I3 transfers
-    int64_t nrot = 0, nrotc = 0;
+    // transfer from level l-1, as TransferPlan describes it (batch-global indices): the explicit lists
+    // (pw empty when uw), or with lat the codes from which the kernels compute the indices instead of
+    // streaming ppar / rcol / rwt (off with DDPCA_LATTICE=0); the block entries' two CSRs
+    DevBuf<int32_t> ppar, rslots, rcol;
+    DevBuf<double> pw, rwt;
+    DevBuf<int64_t> roff;
+    DevBuf<uint32_t> ppk, rmsk;
+    DevBuf<int32_t> pstr, rf0, rstr;
     DevBuf<int32_t> rot_row, rot_par, rotc_row, rotc_kid;
     DevBuf<int64_t> rot_ptr, rotc_ptr;
     DevBuf<double> rot_blk, rotc_blk;
@@ -147,10 +106,7 @@ struct LevelDev {
 // colour by colour); the residual after it is r_i = -U_i x exactly (the row's own equation is
 // met), so sweep + residual cost one operator pass; the backward post-smoothing sweep reads L
 // and U.  With the symmetrised M the V-cycle stays symmetric (pre = forward, post = backward).
-struct GsFine {
-    int ncol = 0;                        // colours
-    int64_t nchunk = 0;                  // colour chunks of the batch, member-major, colour-minor
-    std::vector<int64_t> first, count;   // per colour: its chunk ids in `list`
+struct GsFine : ColourShape {  // (counts, byte model and band flags: ColourShape, mgpis_plan.hpp)
     DevBuf<int32_t> list;                // chunk ids grouped by colour
     DevBuf<int32_t> rowidx;              // per chunk lane: device row, ~first row of the chunk on pad lanes
     DevBuf<int32_t> csub, nsl, nsu;      // per chunk: member, L slots, U slots
@@ -174,23 +130,6 @@ struct GsFine {
     DevBuf<float> r4;  // ... and the residual after the forward sweep (PH 1), which the fine restriction reads
     DevBuf<double> partial;              // per colour chunk: the backward sweep's dot partials (their own
                                          // buffer: a split batch's other half writes the Krylov partials meanwhile)
-    std::vector<int64_t> nnzb_sub;       // per member: stored off-diagonal blocks (byte model)
-    std::vector<int64_t> slots_sub;      // per member: L + U slots incl. padding
-    // algorithmic bytes of each launch over the whole batch, in launch order: forward colours
-    // 0..K-1, the residual, backward colours K-1..0 (stored blocks, per-row vectors, every distinct
-    // x entry gathered once; profiles/gs_table.py sets the rocprof / PMC figures beside them)
-    std::vector<double> launch_bytes;
-    std::vector<double> gx_f, gx_b, rows_k;  // per colour: distinct x gathered (forward, backward), rows
-    double gx_r = 0.0;                       // distinct x the residual gathers
-    std::vector<double> gx_u, nl_k, nu_k;    // per colour: distinct U-side x gathered, L / U blocks
-    double gx_l = 0.0, vb = 0.0;             // distinct L-side x over all colours; bytes per stored block
-    // band mode (locally refined fine level): the colours cover only the band -- the
-    // nodes the fine level adds to the next coarser one and their neighbours; two more chunk groups
-    // per member follow the colours: the ring (non-band rows with a band neighbour: their band
-    // columns only, for the residual) and the far rows (no blocks).  first / count then hold ncol + 2
-    // groups; the sweeps run over the colours, k_gs_aux over the ring and far groups.
-    bool band = false;
-    std::vector<int64_t> band_rows_sub, ring_rows_sub, far_rows_sub, ring_nnzb_sub;
 };
 
 class MgpisDevice {

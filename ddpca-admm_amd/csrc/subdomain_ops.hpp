@@ -2,7 +2,7 @@
 // host grid's operators a MgpisDevice member is built from (ddpca_problem_mgpis,
 // ddpca_problem_mgpis_batch and the MCONTACT batch all take it from here).
 #pragma once
-#include "device_mgpis.hpp"
+#include "mgpis_plan.hpp"
 #include "multigrid.hpp"
 
 namespace ddpca {

@@ -1,7 +1,7 @@
 // Sanitizer driver for the host C++ of libddpca_amd (SURVEY §5 "race detection / sanitizers").
 //
 // Built by tests/sanitize/Makefile from the host translation units only (capi_builder, capi_host,
-// capi_multigrid, csearch, errors, lagrange, mass_plan, mcontact, multigrid, multiscale, sparse, writers) with
+// capi_multigrid, csearch, errors, lagrange, mass_plan, mcontact, mgpis_plan, multigrid, multiscale, sparse, writers) with
 // -fsanitize=address,undefined; no device objects, no GPU.  It drives the setup code that produces
 // every GPU operand through the C ABI the tests use:
 //   * the problem generators (BEAM single / DD, the two-block contact frictionless and Coulomb,
@@ -16,24 +16,38 @@
 //   * the result-file writers;
 //   * the surface-mass batch's host setup (mass_plan.cpp, called directly): ELL-64 packing, pair
 //     detection, spectrum bounds against a dense eigensolve, Chebyshev step counts;
+//   * the host setup of an MGPIS device handle (mgpis_plan.cpp, called directly): the SELL-BSR3 level
+//     plan of a two-member batch with and without coordinates, the value records of every storage
+//     type, lattice and explicit transfers, a nine-parent node, the colour plan, the coarse packing;
+//     on the octree above the block transfer entries and the band of the locally refined fine level;
 //   * the refused-argument paths (bad indices, reversed pointers) of those entry points.
 // The reference-comparison harnesses (oracle/ref_multigrid, ref_csearch, ref_refine,
 // ref_lagrange_host) are linked to the same sanitized objects by the Makefile's `ref` target.
 // Exit status 0 and no sanitizer report = clean.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <tuple>
 #include <vector>
 
+#include "common.hpp"
 #include "ddpca_amd.h"
 #include "mass_plan.hpp"
+#include "mgpis_plan.hpp"
+#include "subdomain_ops.hpp"
+
+namespace ddpca {
+MULTIGRID* multigrid_of(ddpca_multigrid_t h, bool* built);  // capi_multigrid.cpp
+}
 
 namespace {
 
 int g_fail = 0;
+void plan_general(const ddpca::MULTIGRID& g);  // the MGPIS plan on run_octree's tree, below
 
 void ok(int rc, const char* what) {
     if (rc < 0) {
@@ -342,6 +356,8 @@ void run_octree() {
     }
     std::printf("{\"case\": \"octree\", \"nodes\": %ld, \"elements\": %zu, \"planSurf\": %ld, \"checksum\": %.6e}\n", (long)nn, nel,
                 (long)nplan, s);
+    bool built = false;
+    plan_general(*ddpca::multigrid_of(g, &built));
     ddpca_multigrid_destroy(g);
 }
 
@@ -538,6 +554,534 @@ void run_mass_plan() {
                 P.lam_hi[0], lmin, lmax, (long long)K);
 }
 
+// ---- MgpisDevice's host setup (mgpis_plan.cpp), called directly
+using namespace ddpca;
+
+void pcheck(bool good, const char* what) {
+    if (!good) {
+        std::fprintf(stderr, "FAIL mgpis_plan: %s\n", what);
+        ++g_fail;
+    }
+}
+
+// A symmetric operator with nonsymmetric blocks on nodes at integer positions xyz, reference
+// numbering: every pair within one step per axis (and, `far`, the listed extra pairs) coupled by
+// -(M_d + N_d), M_d = I + d d^T / 4 |d|^2 even in d, N_d = 0.05 [d]_x odd in d, so block (j, i) is
+// the transpose of block (i, j); diagonal blocks 30 I plus a symmetric part that varies by node.
+Bsr3 coupled_op(const std::vector<std::array<int, 3>>& xyz, const std::vector<std::pair<int, int>>& far = {}) {
+    const int64_t n = (int64_t)xyz.size();
+    Bsr3 A;
+    A.nb = A.mb = n;
+    A.ptr.assign(1, 0);
+    auto coupled = [&](int64_t i, int64_t j) {
+        for (const auto& f : far)
+            if ((f.first == i && f.second == j) || (f.first == j && f.second == i)) return true;
+        for (int a = 0; a < 3; ++a)
+            if (std::abs(xyz[i][a] - xyz[j][a]) > 1) return false;
+        return true;
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        for (int64_t j = 0; j < n; ++j) {
+            if (!coupled(i, j)) continue;
+            double d[3], b[9];
+            for (int a = 0; a < 3; ++a) d[a] = (double)(xyz[j][a] - xyz[i][a]);
+            if (i == j) {
+                for (int a = 0; a < 3; ++a)
+                    for (int c = 0; c < 3; ++c) b[3 * a + c] = (a == c ? 30.0 : 0.0) + 0.3 * std::sin(1.0 + (double)i + a + c);
+            } else {
+                const double d2 = std::max(1.0, d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+                const double N[9] = {0, -d[2], d[1], d[2], 0, -d[0], -d[1], d[0], 0};
+                for (int a = 0; a < 3; ++a)
+                    for (int c = 0; c < 3; ++c) b[3 * a + c] = -((a == c ? 1.0 : 0.0) + 0.25 * d[a] * d[c] / d2 + 0.05 * N[3 * a + c]) / d2;
+            }
+            A.col.push_back((int32_t)j);
+            A.val.insert(A.val.end(), b, b + 9);
+        }
+        A.ptr.push_back((int64_t)A.col.size());
+    }
+    return A;
+}
+
+// an n0 x n1 x n2 lattice, and its nodes renumbered level-ordered: those at even positions first, in
+// the coarse lattice's lexicographic order (the reference numbering of a once-refined box)
+std::vector<std::array<int, 3>> lattice_xyz(int n0, int n1, int n2, bool level_ordered) {
+    std::vector<std::array<int, 3>> even, odd;
+    for (int z = 0; z < n2; ++z)
+        for (int y = 0; y < n1; ++y)
+            for (int x = 0; x < n0; ++x)
+                (level_ordered && (x % 2 || y % 2 || z % 2) ? odd : even).push_back({x, y, z});
+    even.insert(even.end(), odd.begin(), odd.end());
+    return even;
+}
+
+std::vector<double> as_coords(const std::vector<std::array<int, 3>>& xyz) {
+    std::vector<double> c;
+    for (const auto& p : xyz) c.insert(c.end(), {(double)p[0], (double)p[1], (double)p[2]});
+    return c;
+}
+
+// trilinear stencil from the nodes at even positions (the first nc of xyz, doubled coarse positions)
+Stencil trilinear(const std::vector<std::array<int, 3>>& xyz, int64_t nc) {
+    Stencil S;
+    S.nf = (int64_t)xyz.size();
+    S.nc = nc;
+    S.ptr.assign(1, 0);
+    for (const auto& f : xyz) {
+        for (int64_t c = 0; c < nc; ++c) {
+            double w = 1.0;
+            for (int a = 0; a < 3; ++a) w *= xyz[c][a] == f[a] ? 1.0 : std::abs(xyz[c][a] - f[a]) == 1 ? 0.5 : 0.0;
+            for (int a = 0; a < 3; ++a) w *= f[a] % 2 == 0 && xyz[c][a] != f[a] ? 0.0 : 1.0;
+            if (w != 0.0) S.col.push_back((int32_t)c), S.w.push_back(w);
+        }
+        S.ptr.push_back((int64_t)S.col.size());
+    }
+    return S;
+}
+
+double half_value(uint16_t h) {  // IEEE half -> double
+    const int e = (h >> 10) & 31, m = h & 1023;
+    const double v = e ? std::ldexp(1024.0 + m, e - 25) : std::ldexp((double)m, -24);
+    return h & 0x8000 ? -v : v;
+}
+
+// block (slot, lane) of V, decoded from the layout as the kernels read it
+void decode(const BlockValues& V, int64_t slot, int64_t lane, double* out) {
+    if (V.vt == kValQ8) {
+        const uint8_t* s = V.v8.data() + slot * 768;
+        auto byte = [&](int k) { return s[256 * (k / 4) + 4 * lane + k % 4]; };
+        const uint32_t bits = (uint32_t)byte(9) << 8 | (uint32_t)byte(10) << 16 | (uint32_t)byte(11) << 24;
+        float sc;
+        std::memcpy(&sc, &bits, 4);
+        for (int k = 0; k < 9; ++k) out[k] = (double)sc * (double)(int8_t)byte(k);
+    } else if (V.vt == kValH16) {
+        const uint16_t* s = V.v16.data() + slot * 640;
+        auto half = [&](int k) { return s[128 * (k / 2) + 2 * lane + k % 2]; };
+        for (int k = 0; k < 9; ++k) out[k] = std::ldexp(half_value(half(k)), (int)(int16_t)half(9));
+    } else if (V.vt == kVal32) {
+        for (int k = 0; k < 9; ++k) out[k] = (double)V.v32[slot * 576 + slot_elem<float>(k, lane)];
+    } else {
+        for (int k = 0; k < 9; ++k) out[k] = V.v64[slot * 576 + slot_elem<double>(k, lane)];
+    }
+}
+
+// the dense matrix a level plan's SELL arrays hold (3 nn square; pad slots add their zeros)
+std::vector<double> sell_dense(const LevelPlan& P) {
+    const int64_t n = 3 * P.nn;
+    std::vector<double> D(n * n, 0.0);
+    for (int64_t g = 0; g < P.nn; ++g)
+        for (int64_t q = P.off[g / 64]; q < P.off[g / 64 + 1]; ++q)
+            for (int ij = 0; ij < 9; ++ij)
+                D[(3 * g + ij / 3) * n + 3 * P.col[q * 64 + g % 64] + ij % 3] += P.val[(q * 9 + ij) * 64 + g % 64];
+    return D;
+}
+
+void plan_levels_and_records() {
+    // two members of 37 and 70 nodes on level 1 (8 and 12 on level 0), positions in a 5 x 4 x 4 box;
+    // member 0's node 3 is clamped in y only, member 1's node 0 fully
+    const auto box = lattice_xyz(5, 4, 4, false);
+    const std::vector<std::array<int, 3>> x0(box.begin(), box.begin() + 37), x1(box.begin(), box.begin() + 70);
+    const Bsr3 K0 = coupled_op(x0), K1 = coupled_op(x1);
+    const Bsr3 C0 = coupled_op({x0.begin(), x0.begin() + 8}), C1 = coupled_op({x1.begin(), x1.begin() + 12});
+    const std::vector<double> c0 = as_coords(x0), c1 = as_coords(x1);
+    std::vector<uint8_t> f0(3 * 37, 1), f1(3 * 70, 1);
+    f0[3 * 3 + 1] = 0;
+    f1[0] = f1[1] = f1[2] = 0;
+    for (int with_coords = 0; with_coords < 2; ++with_coords) {
+        std::vector<SubdomainOps> subs(2);
+        subs[0].nnodes = {8, 37};
+        subs[1].nnodes = {12, 70};
+        subs[0].K = {&C0, &K0};
+        subs[1].K = {&C1, &K1};
+        subs[0].dof_free = f0.data();
+        subs[1].dof_free = f1.data();
+        if (with_coords) subs[0].coords = c0.data(), subs[1].coords = c1.data();
+        const MgpisNumbering num = mgpis_numbering(subs, 0);
+        const MgpisTuning tune;
+        const LevelPlan P = plan_level(subs, num, 1, true, 0, tune);
+        pcheck(P.nn == 192 && P.nch == 3 && P.noff == std::vector<int64_t>({0, 64}) && P.csub == std::vector<int32_t>({0, 1, 1}),
+               "37 + 70 nodes pad to 64 + 128, the second member spans two chunks");
+        // the masked operator, restated: identity on constrained dofs
+        const int64_t n = 3 * P.nn;
+        std::vector<double> E(n * n, 0.0);
+        bool pads = true, inv = true;
+        for (int s = 0; s < 2; ++s) {
+            const Bsr3& A = *subs[s].K[1];
+            const uint8_t* fr = subs[s].dof_free;
+            const auto& p = num.perm[1][s];
+            for (int64_t r = 0; r < A.nb; ++r)
+                for (int64_t k = A.ptr[r]; k < A.ptr[r + 1]; ++k)
+                    for (int ij = 0; ij < 9; ++ij) {
+                        const int64_t j = A.col[k], a = ij / 3, b = ij % 3;
+                        const bool fr_ab = fr[3 * r + a] && fr[3 * j + b];
+                        E[(3 * (P.noff[s] + p[r]) + a) * n + 3 * (P.noff[s] + p[j]) + b] =
+                            fr_ab ? A.val[9 * k + ij] : (j == r && a == b ? 1.0 : 0.0);
+                    }
+            // slots past a row's blocks and pad rows: a self column (their values are zero by the dense equality)
+            for (int64_t g = P.noff[s]; g < P.noff[s] + pad64(P.nloc[s]); ++g) {
+                int64_t others = 0, want = 0;
+                for (int64_t q = P.off[g / 64]; q < P.off[g / 64 + 1]; ++q) others += P.col[q * 64 + g % 64] != g;
+                for (int64_t r = 0; r < A.nb; ++r)
+                    if (P.noff[s] + p[r] == g) want = A.ptr[r + 1] - A.ptr[r] - 1;
+                pads = pads && others == want;
+            }
+            // minv x the padded diagonal block: identity on free dofs, zero elsewhere
+            for (int64_t r = 0; r < A.nb; ++r) {
+                const int64_t g = P.noff[s] + p[r];
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < 3; ++b) {
+                        double sum = 0.0;
+                        for (int c = 0; c < 3; ++c) sum += P.minv[9 * g + 3 * a + c] * E[(3 * g + c) * n + 3 * g + b];
+                        const bool fr_ab = fr[3 * r + a] && fr[3 * r + b];
+                        inv = inv && (fr_ab ? std::fabs(sum - (a == b)) <= 1e-12 : P.minv[9 * g + 3 * a + b] == 0.0);
+                    }
+            }
+        }
+        pcheck(sell_dense(P) == E, "decoding the SELL gives the masked operator exactly");
+        pcheck(pads, "pad slots and pad rows carry a self column");
+        pcheck(inv, "minv times the diagonal block is the identity on free dofs, zero elsewhere");
+        bool c16 = P.col16.size() == P.col.size(), sym = true;
+        for (size_t i = 0; c16 && i < P.col.size(); ++i) {
+            const int64_t q = (int64_t)i / 64, c = std::upper_bound(P.off.begin(), P.off.end(), q) - P.off.begin() - 1;
+            c16 = P.col16[i] == P.col[i] - (c * 64 + (int64_t)i % 64);
+        }
+        pcheck(c16, "col16 is col minus the row index");
+        const std::vector<float> m32 = smoother_inverse_fp32(P.minv, true, true);
+        for (int64_t g = 0; g < P.nn; ++g)
+            for (int a = 0; a < 3; ++a)
+                for (int b = 0; b < 3; ++b) sym = sym && m32[9 * g + 3 * a + b] == m32[9 * g + 3 * b + a];
+        pcheck(sym, "minv32 is exactly symmetric");
+        // records: each storage type within its bound of val; fp64 exact
+        for (int vt : {kVal64, kVal32, kValH16, kValQ8}) {
+            const BlockValues V = pack_values(P, vt);
+            bool bound = V.ok;
+            for (int64_t q = 0; q < P.nslots; ++q)
+                for (int64_t lane = 0; lane < 64; ++lane) {
+                    double v[9], d[9], m = 0.0;
+                    for (int k = 0; k < 9; ++k) v[k] = P.val[(q * 9 + k) * 64 + lane], m = std::max(m, std::fabs(v[k]));
+                    decode(V, q, lane, d);
+                    for (int k = 0; k < 9; ++k) {
+                        const double e = std::fabs(d[k] - v[k]);
+                        bound = bound && (vt == kVal64 ? e == 0.0 : vt == kVal32 ? e <= std::ldexp(std::fabs(v[k]), -24)
+                                                          : vt == kValH16 ? e <= std::ldexp(m, -11) : e <= 0.5 * m / 127.0);
+                    }
+                }
+            pcheck(bound, "a value copy lies within its format's bound of val");
+        }
+        // the record of block (i, j) is the transpose of the record of block (j, i): compare the
+        // stored halves / bytes, exponent and scale included
+        for (int vt : {kValH16, kValQ8}) {
+            const BlockValues V = pack_values(P, vt);
+            const int nv = vt == kValQ8 ? 12 : 10;
+            auto rec = [&](int64_t q, int64_t lane, int k) -> int {
+                return vt == kValQ8 ? V.v8[q * 768 + 256 * (k / 4) + 4 * lane + k % 4] : V.v16[q * 640 + 128 * (k / 2) + 2 * lane + k % 2];
+            };
+            bool tr = true;
+            int64_t pairs = 0;
+            for (int64_t g = 64; g < 64 + 70; ++g)  // member 1's rows that couple only free nodes
+                for (int64_t q = P.off[g / 64]; q < P.off[g / 64 + 1]; ++q) {
+                    const int64_t j = P.col[q * 64 + g % 64];
+                    if (j == g || !(P.mask[g] == 7 && P.mask[j] == 7)) continue;
+                    for (int64_t q2 = P.off[j / 64]; q2 < P.off[j / 64 + 1]; ++q2) {
+                        if (P.col[q2 * 64 + j % 64] != g) continue;
+                        ++pairs;
+                        for (int k = 0; k < nv; ++k) tr = tr && rec(q, g % 64, k) == rec(q2, j % 64, k < 9 ? 3 * (k % 3) + k / 3 : k);
+                    }
+                }
+            pcheck(tr && pairs > 100, "the record of block (i, j) is the transpose of that of block (j, i)");
+        }
+        // coarse: member 0's level-1 operator as a dense coarse matrix
+        if (!with_coords) {
+            std::vector<double> D = coarse_dense(subs[0], 1, num.perm[1][0], false), packed;
+            const int64_t ld = coarse_pack(D, subs[0], 1, num.perm[1][0], 64, packed);
+            bool zero = true;
+            for (int64_t e = 0; e < 111; ++e) zero = zero && packed[(3 * 3 + 1) * ld + e] == 0.0 && packed[e * ld + 3 * 3 + 1] == 0.0;
+            pcheck(ld == 112 && packed.size() == (size_t)(111 * 112) && zero && packed[0] == K0.val[0],
+                   "packed coarse rows: stride a multiple of 4, constrained rows and columns zero");
+            bool thrown = false;
+            try {
+                coarse_pack(D, subs[0], 1, num.perm[1][0], 37, packed);  // 112 > 3 * 37
+            } catch (const ApiError& e) {
+                thrown = e.code == DDPCA_ESTATE;
+            }
+            pcheck(thrown, "coarse row padding beyond the member is refused");
+        }
+    }
+    // a block past the int8 record's range: no int8 copy, the level falls back to block-exponent fp16.
+    // Entries of 1e39 are beyond fp32's largest number, which the packing refuses; at 1e41 the scale
+    // max / 127 itself is no fp32 number any more
+    for (double huge : {1e41, 1e39}) {
+        Bsr3 B = coupled_op(x0);
+        for (int k = 0; k < 9; ++k) B.val[9 * B.ptr[5] + k] = huge;
+        std::vector<SubdomainOps> subs(1);
+        subs[0].nnodes = {37};
+        subs[0].K = {&B};
+        std::vector<uint8_t> fr(3 * 37, 1);
+        subs[0].dof_free = fr.data();
+        const MgpisNumbering num = mgpis_numbering(subs, 0);
+        const MgpisTuning tune;
+        const LevelPlan P = plan_level(subs, num, 0, true, 0, tune);
+        const BlockValues V8 = pack_values(P, kValQ8);
+        const int fell_to = level_copy(P, kValQ8, 0, tune).vt;
+        std::printf("{\"case\": \"mgpis_plan_int8_range\", \"entries\": %g, \"int8_ok\": %d, \"level_copy\": %d}\n", huge, (int)V8.ok, fell_to);
+        const std::string at = "entries of " + std::to_string((int)std::log10(huge)) + " decades: ";
+        pcheck(!V8.ok, (at + "int8 packing reports a scale out of range").c_str());
+        pcheck(level_copy_type(3, 2, 3, tune) == kValQ8 && fell_to == kValH16, (at + "the level falls back to fp16").c_str());
+        MgpisTuning t1;
+        t1.h16_levels = 1;
+        t1.q8_levels = 0;
+        t1.col16 = false;
+        pcheck(!P.col16.empty() && plan_level(subs, num, 0, true, 0, t1).col16.empty(), "the tuning switches col16 off");
+        pcheck(level_copy_type(3, 1, 3, t1) == kVal32 && level_copy_type(3, 2, 3, t1) == kValH16 && level_copy_type(1, 2, 3, tune) == kVal32,
+               "copy types follow the tuning's level counts");
+    }
+    // a chain of 33,000 nodes with one block coupling nodes 0 and 32,900: no 16-bit columns
+    {
+        Bsr3 A;
+        A.nb = A.mb = 33000;
+        A.ptr.assign(1, 0);
+        const double I[9] = {4, 0, 0, 0, 4, 0, 0, 0, 4}, O[9] = {-1, 0, 0, 0, -1, 0, 0, 0, -1};
+        for (int64_t i = 0; i < 33000; ++i) {
+            std::vector<int64_t> cols = {i};
+            if (i > 0) cols.push_back(i - 1);
+            if (i + 1 < 33000) cols.push_back(i + 1);
+            if (i == 0) cols.push_back(32900);
+            if (i == 32900) cols.push_back(0);
+            std::sort(cols.begin(), cols.end());
+            for (int64_t j : cols) A.col.push_back((int32_t)j), A.val.insert(A.val.end(), j == i ? I : O, (j == i ? I : O) + 9);
+            A.ptr.push_back((int64_t)A.col.size());
+        }
+        std::vector<SubdomainOps> subs(1);
+        subs[0].nnodes = {33000};
+        subs[0].K = {&A};
+        std::vector<uint8_t> fr(3 * 33000, 1);
+        subs[0].dof_free = fr.data();
+        const MgpisNumbering num = mgpis_numbering(subs, 0);
+        const LevelPlan P = plan_level(subs, num, 0, false, 0, MgpisTuning());
+        pcheck(P.col16.empty() && P.minv.size() == (size_t)(3 * P.nn), "an offset of 32,900 leaves no col16");
+    }
+    // clev: the 256 MB / 12,288-row rule and the option
+    {
+        auto clev = [](std::vector<std::vector<int64_t>> nn, int opt) {
+            std::vector<SubdomainOps> subs(nn.size());
+            for (size_t s = 0; s < nn.size(); ++s) subs[s].nnodes = nn[s];
+            int64_t n0 = 0;
+            const int c = choose_coarse_level(subs, opt, &n0);
+            return std::make_pair(c, n0);
+        };
+        const std::vector<int64_t> a = {10, 1000, 1500, 100000}, b = {10, 3000, 5000, 100000};
+        pcheck(clev({a}, -1) == std::make_pair(2, (int64_t)4500), "one member: 162 MB on level 2 fits");
+        pcheck(clev({a, a}, -1).first == 1, "two members: 324 MB do not, 144 MB on level 1 do");
+        pcheck(clev({b}, -1).first == 0, "15,000 rows are too many, 648 MB too much");
+        pcheck(clev({a}, 1).first == 1 && clev({a}, 9).first == 2 && clev({{50}}, -1) == std::make_pair(0, (int64_t)150),
+               "the option, capped below the fine level; one level");
+    }
+}
+
+// P of a transfer plan's explicit lists, dense (fine device node x coarse device node), and R
+// from its child SELL
+void lists_dense(const TransferPlan& T, const LevelShape& F, const LevelShape& C, std::vector<double>& P, std::vector<double>& R) {
+    P.assign(F.nn * C.nn, 0.0);
+    R.assign(C.nn * F.nn, 0.0);
+    for (int64_t gf = 0; gf < F.nn; ++gf)
+        for (int k = 0; k < 8 && T.ppar[k * F.nn + gf] >= 0; ++k) P[gf * C.nn + T.ppar[k * F.nn + gf]] += T.pw[k * F.nn + gf];
+    for (int64_t j = 0; j < C.nn; ++j)
+        for (int64_t q = T.roff[j / 64]; q < T.roff[j / 64 + 1]; ++q) R[j * F.nn + T.rcol[q * 64 + j % 64]] += T.rwt[q * 64 + j % 64];
+}
+
+void plan_transfers_and_colours() {
+    // 3 x 3 x 3 -> 5 x 5 x 5, trilinear, the fine nodes level-ordered
+    const auto xf = lattice_xyz(5, 5, 5, true);
+    const Bsr3 Kf = coupled_op(xf), Kc = coupled_op({xf.begin(), xf.begin() + 27});
+    Stencil S = trilinear(xf, 27);
+    const std::vector<double> coords = as_coords(xf);
+    std::vector<uint8_t> fr(3 * 125, 1);
+    std::vector<SubdomainOps> subs(1);
+    subs[0].nnodes = {27, 125};
+    subs[0].K = {&Kc, &Kf};
+    subs[0].S = {&S};
+    subs[0].dof_free = fr.data();
+    subs[0].coords = coords.data();
+    const MgpisNumbering num = mgpis_numbering(subs, 0);
+    MgpisTuning tune;
+    const LevelPlan PC = plan_level(subs, num, 0, true, 0, tune), PF = plan_level(subs, num, 1, true, 0, tune);
+    const TransferPlan TL = plan_transfer(subs, num, 1, PF, PC, tune);
+    tune.lattice = false;
+    const TransferPlan TX = plan_transfer(subs, num, 1, PF, PC, tune);
+    tune.lattice = true;
+    pcheck(TL.lat && TL.uw && TL.nrot == 0, "the trilinear lattice is taken as a lattice");
+    pcheck(!TX.lat && TX.uw && TX.ppar == TL.ppar && TX.rcol == TL.rcol, "lattice flag off: explicit lists, uniform averaging");
+    std::vector<double> P, R, E(PF.nn * PC.nn, 0.0);
+    lists_dense(TX, PF, PC, P, R);
+    for (int64_t i = 0; i < 125; ++i)
+        for (int64_t e = S.ptr[i]; e < S.ptr[i + 1]; ++e) E[num.perm[1][0][i] * PC.nn + num.perm[0][0][S.col[e]]] = S.w[e];
+    bool rt = true, codes = true;
+    for (int64_t gf = 0; gf < PF.nn; ++gf)
+        for (int64_t j = 0; j < PC.nn; ++j) rt = rt && R[j * PF.nn + gf] == P[gf * PC.nn + j];
+    pcheck(P == E, "the lists applied as P reproduce the stencil exactly");
+    pcheck(rt, "the child SELL applied as R is P^T exactly");
+    // the lattice codes expand to the same parents and children
+    for (int64_t gf = 0; gf < 125 && TL.lat; ++gf) {
+        const uint32_t code = TL.ppk[gf] >> 29, p0 = TL.ppk[gf] & 0x1FFFFFFFu;
+        std::vector<double> row(PC.nn, 0.0);
+        const int np = 1 << __builtin_popcount(code);
+        for (uint32_t q = 0; q < 8; ++q)
+            if ((q & ~code) == 0) row[p0 + ((q & 1) ? TL.pstr[0] : 0) + ((q & 2) ? TL.pstr[1] : 0) + ((q & 4) ? TL.pstr[2] : 0)] += 1.0 / np;
+        codes = codes && std::equal(row.begin(), row.end(), E.begin() + gf * PC.nn);
+    }
+    for (int64_t j = 0; j < 27 && TL.lat; ++j) {
+        std::vector<double> row(PF.nn, 0.0);
+        for (int q = 0; q < 27; ++q)
+            if ((TL.rmsk[j] >> q) & 1u) {
+                const int d[3] = {q % 3 - 1, (q / 3) % 3 - 1, q / 9 - 1};
+                row[TL.rf0[j] + d[0] * TL.rstr[0] + d[1] * TL.rstr[1] + d[2] * TL.rstr[2]] += 1.0 / (1 << ((d[0] != 0) + (d[1] != 0) + (d[2] != 0)));
+            }
+        codes = codes && std::equal(row.begin(), row.end(), R.begin() + j * PF.nn);
+    }
+    pcheck(codes, "the lattice codes expand to the lists' parents and children");
+    // not the identity on a coarse node: DDPCA_EINVAL
+    {
+        Stencil B = S;
+        B.w[B.ptr[4]] = 0.5;
+        subs[0].S = {&B};
+        bool thrown = false;
+        try {
+            plan_transfer(subs, num, 1, PF, PC, tune);
+        } catch (const ApiError& e) {
+            thrown = e.code == DDPCA_EINVAL && std::string(e.what()) == "stencil is not identity on coarse nodes";
+        }
+        pcheck(thrown, "a stencil that is not the identity on a coarse node is refused");
+        subs[0].S = {&S};
+    }
+    // a node with nine parents: the ninth goes to the block CSRs as w I
+    {
+        Stencil N;
+        N.nf = 11;
+        N.nc = 10;
+        N.ptr.assign(1, 0);
+        for (int i = 0; i < 10; ++i) N.col.push_back(i), N.w.push_back(1.0), N.ptr.push_back(i + 1);
+        for (int c = 0; c < 9; ++c) N.col.push_back(c), N.w.push_back(1.0 / 9.0);
+        N.ptr.push_back(19);
+        LevelShape F, C;
+        F.nn = C.nn = 64;
+        F.nch = C.nch = 1;
+        F.noff = C.noff = {0};
+        F.nloc = {11};
+        C.nloc = {10};
+        std::vector<SubdomainOps> one(1);
+        one[0].nnodes = {10, 11};
+        one[0].S = {&N};
+        MgpisNumbering id;
+        id.perm = {{identity_order(10)}, {identity_order(11)}};
+        const TransferPlan T = plan_transfer(one, id, 1, F, C, tune);
+        const double w = 1.0 / 9.0;
+        pcheck(!T.uw && !T.lat && T.nrot == 1 && T.nrotc == 1 && T.rot_row == std::vector<int32_t>({10}) &&
+                   T.rot_par == std::vector<int32_t>({8}) && T.rotc_row == std::vector<int32_t>({8}) &&
+                   T.rotc_kid == std::vector<int32_t>({10}) && T.rot_blk == std::vector<double>({w, 0, 0, 0, w, 0, 0, 0, w}) &&
+                   T.ppar[7 * 64 + 10] == 7 && T.tent_sub[0] == 19,
+               "the ninth parent runs as a w I block");
+    }
+    // colours on the 5 x 5 x 5 27-point operator
+    const std::vector<float> m32 = smoother_inverse_fp32(PF.minv, true, true);
+    const ColourPlan G = plan_colours(PF, kValH16, &m32, nullptr, tune);
+    std::vector<int> colour(PF.nn, -1), seen(PF.nn, 0), chunk_colour(G.nchunk, -1);
+    for (int k = 0; k < G.ncol; ++k)
+        for (int64_t i = G.first[k]; i < G.first[k] + G.count[k]; ++i) chunk_colour[G.list[i]] = k;
+    bool pad = true, split = true, proper = true;
+    for (int64_t c = 0; c < G.nchunk; ++c)
+        for (int64_t lane = 0; lane < 64; ++lane) {
+            const int32_t r = G.rowidx[c * 64 + lane];
+            if (r >= 0) colour[r] = chunk_colour[c], ++seen[r];
+            else pad = pad && r == ~G.rowidx[c * 64];
+        }
+    for (int64_t g = 0; g < 125; ++g) pad = pad && seen[g] == 1;
+    for (int64_t c = 0; c < G.nchunk; ++c)
+        for (int64_t lane = 0; lane < 64; ++lane) {
+            const int32_t g = G.rowidx[c * 64 + lane];
+            if (g < 0) continue;
+            std::vector<int64_t> row, lu;
+            for (int64_t q = PF.off[g / 64]; q < PF.off[g / 64 + 1]; ++q)
+                if (PF.col[q * 64 + g % 64] != g) row.push_back(PF.col[q * 64 + g % 64]);
+            for (int64_t q = G.offl[c]; q < G.offl[c] + G.nsl[c] + G.nsu[c]; ++q) {
+                const int64_t j = g + G.col16[q * 64 + lane];
+                if (j == g) continue;  // a pad slot
+                lu.push_back(j);
+                split = split && (colour[j] < colour[g]) == (q < G.offu[c]);
+                proper = proper && colour[j] != colour[g];
+            }
+            std::sort(row.begin(), row.end());
+            std::sort(lu.begin(), lu.end());
+            split = split && row == lu;
+        }
+    pcheck(G.ncol == 8 && proper, "8 colours, no two coupled rows share one");
+    pcheck(pad, "every real row once in rowidx, pad lanes the complement of the chunk's first row");
+    pcheck(split, "L + U + diagonal is the row, L exactly the columns of earlier colours");
+    pcheck(G.launch_bytes.size() == (size_t)(2 * G.ncol + 1) && G.minvc.size() == (size_t)G.nchunk * 576 && !G.band,
+           "launch_bytes has 2 K + 1 entries");
+    ColourShape M = G;
+    colour_byte_model(M, 4, true, true);
+    pcheck(M.launch_bytes.size() == (size_t)(4 * G.ncol + 1), "colour SSOR's model has 4 K + 1 launches");
+    std::printf("{\"case\": \"mgpis_plan\", \"colours\": %d, \"colour_chunks\": %lld, \"lattice\": %d}\n", G.ncol,
+                (long long)G.nchunk, (int)TL.lat);
+}
+
+// the refined octree: block transfer entries (rotated nodes) and the locally refined fine level's band
+void plan_general(const MULTIGRID& g) {
+    const std::vector<SubdomainOps> subs = {subdomain_ops(g)};
+    const int nlev = (int)subs[0].nnodes.size();
+    const MgpisNumbering num = mgpis_numbering(subs, 0);
+    MgpisTuning tune;
+    std::vector<LevelPlan> P;
+    for (int l = 0; l < nlev; ++l) P.push_back(plan_level(subs, num, l, true, 0, tune));
+    int64_t blocks = 0;
+    for (int l = 1; l < nlev; ++l) {
+        const TransferPlan T = plan_transfer(subs, num, l, P[l], P[l - 1], tune);
+        if (subs[0].S[l - 1]->bent.empty()) continue;
+        using Ent = std::tuple<int32_t, int32_t, std::array<double, 9>>;
+        std::vector<Ent> by_f, by_c;
+        auto collect = [](const std::vector<int32_t>& row, const std::vector<int64_t>& ptr, const std::vector<int32_t>& other,
+                          const std::vector<double>& blk, bool fine_rows, std::vector<Ent>& out) {
+            for (size_t r = 0; r < row.size(); ++r)
+                for (int64_t e = ptr[r]; e < ptr[r + 1]; ++e) {
+                    std::array<double, 9> b;
+                    std::copy(blk.begin() + 9 * e, blk.begin() + 9 * e + 9, b.begin());
+                    out.push_back(fine_rows ? Ent{row[r], other[e], b} : Ent{other[e], row[r], b});
+                }
+            std::sort(out.begin(), out.end());
+        };
+        collect(T.rot_row, T.rot_ptr, T.rot_par, T.rot_blk, true, by_f);
+        collect(T.rotc_row, T.rotc_ptr, T.rotc_kid, T.rotc_blk, false, by_c);
+        blocks += (int64_t)by_f.size();
+        pcheck(!T.uw && !T.lat && by_f == by_c && by_f.size() >= subs[0].S[l - 1]->bent.size(),
+               "block entries: no uniform averaging, the same entry set by fine and by coarse node");
+    }
+    pcheck(blocks > 0, "the rotated octree has block transfer entries");
+    const int L = nlev - 1;
+    const std::vector<uint8_t> band = colour_band(subs, num, L, P[L], tune);
+    int64_t nband = 0;
+    for (uint8_t f : band) nband += f != 0;
+    pcheck(!band.empty() && 5 * nband <= 3 * P[L].nloc[0], "the refined corner's band is under 60 % of the rows");
+    if (!band.empty()) {
+        const ColourPlan G = plan_colours(P[L], kVal32, nullptr, &band, tune);
+        pcheck(G.band && (int)G.first.size() == G.ncol + 2 && G.count[G.ncol] > 0 && G.count[G.ncol + 1] > 0 &&
+                   G.band_rows_sub[0] == nband && G.ring_rows_sub[0] > 0 && G.far_rows_sub[0] > 0 &&
+                   nband + G.ring_rows_sub[0] + G.far_rows_sub[0] == P[L].nloc[0],
+               "band mode: the colours cover the band, ring and far groups the rest");
+    }
+    tune.gs_band = false;
+    pcheck(colour_band(subs, num, L, P[L], tune).empty(), "band flag off: no band");
+    const ColourPlan A = plan_colours(P[L], kVal32, nullptr, nullptr, tune);
+    double rows = 0.0;
+    for (double r : A.rows_k) rows += r;
+    pcheck(!A.band && (int)A.first.size() == A.ncol && rows == (double)P[L].nloc[0], "band flag off: the colours sweep every row");
+    std::printf("{\"case\": \"mgpis_plan_general\", \"levels\": %d, \"fine_rows\": %lld, \"band\": %lld, \"block_entries\": %lld}\n",
+                nlev, (long long)P[L].nloc[0], (long long)nband, (long long)blocks);
+}
+
+void run_mgpis_plan() {
+    plan_levels_and_records();
+    plan_transfers_and_colours();
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -573,6 +1117,7 @@ int main(int argc, char** argv) {
     run_csearch();
     run_writers();
     run_mass_plan();
+    run_mgpis_plan();
     std::printf("{\"ok\": %s, \"failures\": %d}\n", g_fail ? "false" : "true", g_fail);
     return g_fail ? 1 : 0;
 }

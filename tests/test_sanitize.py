@@ -6,7 +6,10 @@ pipeline on any octree, both coarse spaces, CSEARCH, CURVEDS/REFINE, the writers
 with -fsanitize=address,undefined and links tests/sanitize/host_driver.cpp, which drives them through
 the C ABI (problems of every generator incl. rank-local builds, a refined curved octree, a contact
 search, the refused-argument paths) and, called directly, the surface-mass batch's host setup
-(mass_plan.cpp: packing, pairing, spectrum bounds, Chebyshev step counts).  A sanitizer report aborts the driver (halt_on_error).  The
+(mass_plan.cpp: packing, pairing, spectrum bounds, Chebyshev step counts) and the host setup of an MGPIS
+device handle (mgpis_plan.cpp, run_mgpis_plan and plan_general in the driver: level packing, value records,
+transfers, colours, coarse packing on the smallest shapes at which each can go wrong).  A sanitizer report
+aborts the driver (halt_on_error).  The
 reference-comparison harnesses of the CPU tests linked to the same objects (`make ref run`:
 ref_multigrid, ref_csearch, ref_refine, ref_lagrange_host, about 5 minutes) ran clean too:
 profiles/r04_sanitize.log."""
