@@ -29,19 +29,14 @@
 
 #include <algorithm>
 #include <chrono>
-#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <memory>
-#include <numeric>
 #include <thread>
-#include <tuple>
-#include <unordered_map>
 
 #include "../../include/ddpca_amd.h"
-#include "csr_ops.hpp"
+#include "admm_plan.hpp"
 #include "device_eigs.hpp"
 #include "device_mass.hpp"
 #include "device_mgpis.hpp"
@@ -467,51 +462,17 @@ __global__ void k_fuse_aux_lambda(double* state, const double* wv, const double*
     state[R + i] = -v;
 }
 
-// Row lists -> SELL-64 (rows padded to a multiple of 64; padding slots: column 0, value 0).
-using Rows = std::vector<std::vector<std::pair<int64_t, double>>>;
-
-struct SellOp {
-    int64_t nrow = 0, nch = 0;
+// A planned SELL-64 operator over W (sell_pack, admm_plan.hpp) on the device.
+struct SellOp : SellShape {
     DevBuf<int32_t> slots, col;
     DevBuf<int64_t> off;
     DevBuf<double> val;
-    // algorithmic bytes of one apply: the stored entries (8 B value + 4 B column), each distinct
-    // gathered W entry once, every real row written once (an `add` operand adds 8 B per row)
-    double bytes = 0.0;
-    void build(const Rows& rows) {
-        nrow = pad64((int64_t)rows.size());
-        nch = nrow / 64;
-        std::vector<int32_t> sl(std::max<int64_t>(nch, 1), 0);
-        std::vector<int64_t> of(nch + 1, 0);
-        for (int64_t c = 0; c < nch; ++c) {
-            size_t mx = 0;
-            for (int64_t r = c * 64; r < std::min<int64_t>((int64_t)rows.size(), (c + 1) * 64); ++r) mx = std::max(mx, rows[r].size());
-            sl[c] = (int32_t)mx;
-            of[c + 1] = of[c] + (int64_t)mx;
-        }
-        std::vector<int32_t> co(std::max<int64_t>(of[nch] * 64, 1), 0);
-        std::vector<double> va(std::max<int64_t>(of[nch] * 64, 1), 0.0);
-        for (int64_t r = 0; r < (int64_t)rows.size(); ++r) {
-            const int64_t c = r / 64, lane = r % 64;
-            for (size_t k = 0; k < rows[r].size(); ++k) {
-                if (rows[r][k].first > INT32_MAX) throw ApiError(DDPCA_EINVAL, "workspace index exceeds int32");
-                co[(of[c] + (int64_t)k) * 64 + lane] = (int32_t)rows[r][k].first;
-                va[(of[c] + (int64_t)k) * 64 + lane] = rows[r][k].second;
-            }
-        }
-        slots.upload(sl);
-        off.upload(of);
-        col.upload(co);
-        val.upload(va);
-        int64_t ent = 0;
-        std::vector<int64_t> cols;
-        for (const auto& r : rows) {
-            ent += (int64_t)r.size();
-            for (const auto& e : r) cols.push_back(e.first);
-        }
-        std::sort(cols.begin(), cols.end());
-        const int64_t uniq = (int64_t)(std::unique(cols.begin(), cols.end()) - cols.begin());
-        bytes = 12.0 * (double)ent + 8.0 * (double)uniq + 8.0 * (double)rows.size();
+    void upload(const SellPlan& P) {
+        static_cast<SellShape&>(*this) = P;
+        slots.upload(P.slots);
+        off.upload(P.off);
+        col.upload(P.col);
+        val.upload(P.val);
     }
     void apply(hipStream_t s, const double* W, double* y, const double* add) const {
         if (nch) hipLaunchKernelGGL(k_sell_w, dim3(ceil_div(nch, 4)), dim3(256), 0, s, slots.p, off.p, col.p, val.p, nch, W, y, add);
@@ -537,9 +498,9 @@ bool two_streams() {
 //   xc = globCoup_1^-1 g, rows of the owned subdomains (dense inverse from rocSOLVER potrf/potri
 //        at setup; the reference factorises with SimplicialLDLT, 2589-2591)
 //   u += OUTP_SUB1(accuProl xc)                                             (2600-2610)
-struct CoarseDev {
+struct CoarseDev : CoarseProlongShape {  // (npr, ncd, nxn, qnn, dmin: admm_plan.hpp)
     bool on = false, inverted = false;
-    int64_t n = 0, nown = 0, nxn = 0, qnn = 0;
+    int64_t n = 0, nown = 0;
     double dense_bytes = 0.0;  // n^2 8 B: what the dense inverse would hold per rank
     bool mg_fallback = false;  // (kept for the "coarse_solve" getter: DOUBLE_M is always buildable now)
     DevBuf<double> g, f0, xc, xn, ainv;
@@ -557,7 +518,6 @@ struct CoarseDev {
         DevBuf<int64_t> src;
     };
     std::vector<KGroup> kg;
-    int dmin = 0;
     DevBuf<int32_t> xsrc, qcol;
     DevBuf<double> qw;
     DevBuf<uint8_t> flag;
@@ -566,7 +526,6 @@ struct CoarseDev {
     // parents) for every node it can hold, CSR rows (same arrays) for the rest -- nodes whose chain
     // meets a nodal rotation's 3x3 block (general trees)
     bool assembled = false, latin = false;
-    int64_t npr = 0, ncd = 0;
     DevBuf<int64_t> pptr;
     DevBuf<int32_t> pcol, ptgt, cdof;
     DevBuf<double> pval;
@@ -582,16 +541,9 @@ struct CoarseDev {
     // hierarchy whose transfers are every subdomain's realProl below doleMcsc, block-diagonal
     bool mg = false;
     bool mg_gather = false;  // a rank-local build: the whole operator is gathered at coarse_invert
-    // the coarse MGPIS's structure (plan_coarse_mg, at setup): nodes per level, transfers, the
-    // coarse rows' dofs, per-level dof flags; kept until the operator is there (finish_coarse_mg)
-    struct MgPlan {
-        std::vector<int64_t> nglob;
-        std::vector<Stencil> S;
-        std::vector<int32_t> fdg;
-        std::vector<std::vector<uint8_t>> flev;
-        bool latin = false;
-        void swap_into(MgPlan& o) { std::swap(*this, o); }
-    } plan;
+    // the coarse MGPIS's structure (plan_coarse_mg, at setup), kept until the operator is there
+    // (finish_coarse_mg)
+    MgPlan plan;
     Csr gathered_rows;  // this rank's rows of a rank-local operator (sent once at coarse_invert)
     std::unique_ptr<MgpisDevice> cmg;
     DevBuf<int32_t> cperm;  // coarse row -> dof of cmg's fine level (device layout)
@@ -604,31 +556,17 @@ struct CoarseDev {
 };
 
 // ================================================================================ handle
-struct ddpca_mcontact {
-    struct Sub {
-        int64_t tv = 0, nn = 0;
-        int64_t dof0 = 0;  // first dof in the batch's fine layout
-        int64_t nh = 0;    // hanging-level dofs (MULTIGRID::hangProl rows), at W[oH + hoff]
-        int64_t hoff = 0;
-        // workspace index of the subdomain's nodal dof c (position numbering, hanging level last)
-        int64_t wcol(int64_t c, int64_t oH) const { return c < 3 * nn ? dof0 + c : oH + hoff + (c - 3 * nn); }
-    };
-    struct Side {
-        int64_t ts = 0, s = 0, tv = 0, m = 0, mip = 0;
-        int64_t roff = 0;  // rows of aux at W[oS + roff], lambda at W[oS + R + roff]
-        int sub = 0;       // index into subs
-    };
-    struct Itf {
-        int64_t ts = 0, mip = 0, goff = 0;
-        int comp = 1;
-        double fric = -1.0;
-        int owner[2] = {0, 0};
-        bool mine = false, cross = false;
+// (the workspace layout W = [u (NU) | u on hanging levels (NH) | aux, lambda (2R) | gamma (G)], nsub
+// and nint: AdmmLayout; the tables' entries: AdmmSub / AdmmSide / AdmmItf, admm_plan.hpp)
+struct ddpca_mcontact : AdmmLayout {
+    using Sub = AdmmSub;
+    using Side = AdmmSide;
+    struct Itf : AdmmItf {
         DevBuf<int32_t> stat;
         DevBuf<double> recv;
     };
     int device = 0, rank = 0, nranks = 1;
-    int64_t nsub = 0, nint = 0;
+    AdmmTuning tune;  // read once at create
     std::vector<int32_t> owner;
     std::vector<Sub> subs;
     std::vector<Side> sides;
@@ -643,10 +581,7 @@ struct ddpca_mcontact {
     DevBuf<int32_t> ccol;                // columns index W
     DevBuf<double> cval;
     int64_t ncrow = 0;
-    int64_t R = 0;                       // padded rows of all owned sides
-    // workspace W = [u (NU) | u on hanging levels (NH) | aux, lambda (2R) | gamma (G)] and its regions
     DevBuf<double> W;
-    int64_t NU = 0, NH = 0, G = 0, oH = 0, oS = 0, oG = 0;
     SellOp op_hang;                      // hanging-level values: rows of prolOper[maxiLeve] over u
     double* u = nullptr;
     double* state = nullptr;
@@ -664,17 +599,12 @@ struct ddpca_mcontact {
     DevBuf<double> gam1;
     DevBuf<int32_t> gam1_dst;
     // interfaces whose per-ip operators are applied in factored form (Interface::factored)
-    struct FactItf {
-        int64_t ts = 0, nip = 0, goff = 0;
-        int C = 1, own[2] = {0, 0};
-        double pen[3] = {0.0, 0.0, 0.0};
+    struct FactItf : FactItfShape {
         DevBuf<double> B, M[2], T;
         DevBuf<int32_t> lam[2], u[2];
-        int64_t nnc[2] = {0, 0}, roff[2] = {0, 0};  // node-major inteInpo (fused update)
         DevBuf<int64_t> nptr[2];
         DevBuf<int32_t> niq[2];
         DevBuf<double> ncoef[2];
-        double bytes_gamma = 0.0, bytes_inpo = 0.0;  // algorithmic bytes of k_gamma_ip / k_traction_ip + k_inpo_node
     };
     std::vector<FactItf> fitfs;
     MassBatch mb_aux, mb_lam;
@@ -717,25 +647,26 @@ struct ddpca_mcontact {
 
 namespace {
 
-void build(ddpca_mcontact& H, Problem& P) {
-    MCONTACT& mc = P.mc;
-    H.nsub = (int64_t)mc.multGrid.size();
-    H.nint = (int64_t)mc.searCont.size();
+// what the plan sees of the owned subdomains' batch (empty without one)
+BatchView batch_view(const MgpisDevice* D) {
+    BatchView V;
+    if (!D) return V;
+    for (const LevelDev& L : D->lev) V.lev.push_back({L.nn, L.noff, L.nloc, L.tent_sub, L.lat});
+    V.level_perm = &D->level_perm;
+    V.nfree = D->nfree;
+    return V;
+}
+
+// The handle's device operands from the established problem: each part planned on the host
+// (admm_plan.hpp), uploaded, its work buffers allocated, the plan dropped.  Returns the tables for
+// build_coarse.
+AdmmTables build(ddpca_mcontact& H, const Problem& P) {
+    const MCONTACT& mc = P.mc;
     // ---- owned subdomains: one batched MGPIS
-    std::vector<SubdomainOps> ops;
-    for (int64_t tv = 0; tv < H.nsub; ++tv) {
-        if (H.owner[tv] != H.rank) continue;
-        if (P.owned.size() != (size_t)H.nsub || !P.owned[tv])
-            throw ApiError(DDPCA_ESTATE, "subdomain " + std::to_string(tv) + " is owned by this rank but was not established");
-        const MULTIGRID& g = mc.multGrid[tv];
-        ops.push_back(subdomain_ops(g));
-        ddpca_mcontact::Sub S;
-        S.tv = tv;
-        S.nn = g.leveCount.back();
-        S.nh = 3 * (g.nodalCount() - S.nn);
-        H.subs.push_back(S);
-    }
-    if (!ops.empty()) {
+    std::vector<AdmmSub> subs = owned_subdomains(P, H.owner, H.rank);
+    if (!subs.empty()) {
+        std::vector<SubdomainOps> ops;
+        for (const auto& S : subs) ops.push_back(subdomain_ops(mc.multGrid[S.tv]));
         H.mg = std::make_unique<MgpisDevice>(H.device, ops, H.opt);
         H.main = H.mg->stream;
         // the body balance's batch on two streams (MgpisDevice::set_split); DDPCA_STREAMS=1 keeps
@@ -745,90 +676,29 @@ void build(ddpca_mcontact& H, Problem& P) {
     } else {
         DDPCA_HIP(hipStreamCreateWithFlags(&H.main, hipStreamNonBlocking));
     }
-    auto sub_index = [&](int64_t tv) {
-        for (size_t i = 0; i < H.subs.size(); ++i)
-            if (H.subs[i].tv == tv) return (int)i;
-        return -1;
-    };
-    const int64_t NN = H.mg ? H.mg->lev.back().nn : 0;
-    H.NU = std::max<int64_t>(3 * NN, 64);
-    for (auto& S : H.subs) {
-        S.hoff = H.NH;
-        H.NH += S.nh;
-    }
-    H.NH = pad64(H.NH);
-    {
-        std::vector<double> cf(H.NU, 0.0), pr(H.NU, 0.0);
-        std::vector<int32_t> on(std::max<int64_t>(NN, 1));
-        std::iota(on.begin(), on.end(), 0);  // padding nodes map to themselves
-        for (size_t i = 0; i < H.subs.size(); ++i) {
-            auto& S = H.subs[i];
-            S.dof0 = H.mg->fine_dof_offset((int)i);
-            // DDPCA_PCG_MAXIT (diagnostics only): cap the body solves below the reference's maxit = rows
-            static const int64_t cap = std::getenv("DDPCA_PCG_MAXIT") ? std::atoll(std::getenv("DDPCA_PCG_MAXIT")) : 0;
-            H.maxit.push_back(cap > 0 ? std::min<int64_t>(cap, H.mg->nfree[i]) : H.mg->nfree[i]);
-            const MULTIGRID& g = mc.multGrid[S.tv];
-            for (int64_t d = 0; d < 3 * S.nn; ++d)
-                if (g.consFlag[d]) cf[H.mg->fine_dof((int)i, d)] = g.consForc[g.freeIndex[d]];
-            for (const auto& kv : g.consDofv) pr[S.dof0 + kv.first] = kv.second;
-            for (int64_t r = 0; r < S.nn; ++r) on[S.dof0 / 3 + H.mg->fine_perm[i][r]] = (int32_t)(S.dof0 / 3 + r);
+    const BatchView V = batch_view(H.mg.get());
+    // ---- tables: subdomains, owned sides, interfaces, the regions of W
+    AdmmTables T = plan_tables(mc, std::move(subs), H.owner, H.rank, V, H.tune);
+    static_cast<AdmmLayout&>(H) = T;
+    H.subs = T.subs;
+    H.sides = T.sides;
+    H.maxit = T.maxit;
+    H.cf.upload(T.cf);
+    H.presc.upload(T.presc);
+    H.onode.upload(T.onode);
+    std::vector<double>().swap(T.cf);
+    std::vector<double>().swap(T.presc);
+    std::vector<int32_t>().swap(T.onode);
+    for (const AdmmItf& t : T.itfs) {
+        ddpca_mcontact::Itf I;
+        static_cast<AdmmItf&>(I) = t;
+        if (I.mine) {
+            I.stat.alloc(std::max<int64_t>(I.mip / I.comp, 1));
+            if (I.cross) I.recv.alloc(I.mip);
         }
-        H.cf.upload(cf);
-        H.presc.upload(pr);
-        H.onode.upload(on);
+        H.itfs.push_back(std::move(I));
     }
-    // ---- owned interface sides: aux rows [roff, roff + m), lambda rows R + the same
-    int64_t roff = 0;
-    std::map<std::pair<int64_t, int64_t>, size_t> side_of;
-    for (int64_t ts = 0; ts < H.nint; ++ts) {
-        const Interface& itf = mc.searCont[ts];
-        for (int s = 0; s < 2; ++s) {
-            if (H.owner[itf.body[s]] != H.rank) continue;
-            ddpca_mcontact::Side sd;
-            sd.ts = ts;
-            sd.s = s;
-            sd.tv = itf.body[s];
-            sd.sub = sub_index(sd.tv);
-            sd.m = itf.mside(s);
-            sd.mip = itf.mip();
-            sd.roff = roff;
-            roff += pad64(sd.m);
-            side_of[{ts, s}] = H.sides.size();
-            H.sides.push_back(sd);
-        }
-    }
-    H.R = roff;
-    // ---- interfaces: gamma layout (cross-rank interfaces first, then rank-local)
-    int64_t goff = 0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int64_t ts = 0; ts < H.nint; ++ts) {
-            const Interface& itf = mc.searCont[ts];
-            const int o0 = H.owner[itf.body[0]], o1 = H.owner[itf.body[1]];
-            const bool cross = o0 != o1;
-            if ((pass == 0) != cross) continue;
-            ddpca_mcontact::Itf I;
-            I.ts = ts;
-            I.mip = itf.mip();
-            I.comp = itf.comp();
-            I.fric = itf.fric;
-            I.owner[0] = o0;
-            I.owner[1] = o1;
-            I.cross = cross;
-            I.mine = (o0 == H.rank || o1 == H.rank);
-            I.goff = goff;
-            goff += I.mip;
-            if (I.mine) {
-                I.stat.alloc(std::max<int64_t>(I.mip / I.comp, 1));
-                if (cross) I.recv.alloc(I.mip);
-            }
-            H.itfs.push_back(std::move(I));
-        }
-    std::sort(H.itfs.begin(), H.itfs.end(), [](const auto& a, const auto& b) { return a.ts < b.ts; });
-    H.G = pad64(std::max<int64_t>(goff, 1));
     // ---- workspace
-    H.oH = H.NU;
-    H.oS = H.NU + H.NH;
-    H.oG = H.oS + 2 * H.R;
     H.W.alloc(H.oG + H.G);
     H.W.zero(H.main);
     H.u = H.W.p;
@@ -838,310 +708,83 @@ void build(ddpca_mcontact& H, Problem& P) {
     H.uo.zero(H.main);
     H.state_old.alloc(std::max<int64_t>(2 * H.R, 2));
     H.state_old.zero(H.main);
-    auto itf_of = [&](int64_t ts) -> const ddpca_mcontact::Itf& {
-        return *std::find_if(H.itfs.begin(), H.itfs.end(), [&](const auto& x) { return x.ts == ts; });
-    };
     // ---- factored per-ip operators of host-built interfaces this rank handles
-    for (const auto& I : H.itfs) {
-        const Interface& itf = mc.searCont[I.ts];
-        if (!I.mine || !itf.factored) continue;
-        ddpca_mcontact::FactItf F;
-        F.ts = I.ts;
-        F.nip = (int64_t)itf.ip.size();
-        F.goff = I.goff;
-        F.C = itf.comp();
-        for (int m = 0; m < F.C; ++m) F.pen[m] = itf.pemaDiag[m];  // pemaDiag[C q + m] = pen[m] for every q
-        const int64_t nip = F.nip;
-        std::vector<double> B(9 * std::max<int64_t>(nip, 1));
-        for (int64_t q = 0; q < nip; ++q)
-            for (int j = 0; j < 9; ++j) B[j * nip + q] = itf.ip[q].basis[j / 3][j % 3];
-        F.B.upload(B);
-        F.T.alloc(std::max<int64_t>(F.C * nip, 1));
+    for (const AdmmItf& I : T.itfs) {
+        if (!I.mine || !mc.searCont[I.ts].factored) continue;
+        const FactItfPlan F = plan_factored(mc, T, I);
+        ddpca_mcontact::FactItf D;
+        static_cast<FactItfShape&>(D) = F;
+        D.B.upload(F.B);
+        D.T.alloc(std::max<int64_t>(F.C * F.nip, 1));
         for (int s = 0; s < 2; ++s) {
-            if (H.owner[itf.body[s]] != H.rank) continue;
-            F.own[s] = 1;
-            const auto& sd = H.sides[side_of.at({I.ts, s})];
-            const auto& Su = H.subs[sd.sub];
-            const int64_t lam0 = H.oS + H.R + sd.roff;
-            std::unordered_map<int64_t, int32_t> cidx;
-            for (size_t a = 0; a < itf.nodeCont[s].size(); ++a) cidx.emplace(itf.nodeCont[s][a], (int32_t)a);
-            std::vector<double> M(4 * std::max<int64_t>(nip, 1));
-            std::vector<int32_t> lam(4 * std::max<int64_t>(nip, 1)), u(4 * std::max<int64_t>(nip, 1));
-            std::vector<std::vector<std::pair<int32_t, double>>> bynode(itf.nodeCont[s].size());
-            const double sgn = s == 0 ? -1.0 : 1.0;  // inteInpo's sign (mcontact.cpp BUILD)
-            for (int64_t q = 0; q < nip; ++q)
-                for (int a = 0; a < 4; ++a) {
-                    const int64_t node = itf.ip[q].node[s][a];
-                    const int32_t c = cidx.at(node);
-                    M[a * nip + q] = itf.ip[q].shap[s][a];
-                    lam[a * nip + q] = (int32_t)(lam0 + F.C * c);
-                    u[a * nip + q] = (int32_t)Su.wcol(3 * node, H.oH);
-                    bynode[c].push_back({(int32_t)q, sgn * (itf.ip[q].w * itf.ip[q].shap[s][a])});
-                }
-            F.M[s].upload(M);
-            F.lam[s].upload(lam);
-            F.u[s].upload(u);
-            std::vector<int64_t> ptr{0};
-            std::vector<int32_t> iq;
-            std::vector<double> coef;
-            for (const auto& v : bynode) {
-                for (const auto& e : v) {
-                    iq.push_back(e.first);
-                    coef.push_back(e.second);
-                }
-                ptr.push_back((int64_t)iq.size());
-            }
-            F.nnc[s] = (int64_t)bynode.size();
-            F.roff[s] = sd.roff;
-            // k_gamma_ip's share of this side: shape values, lambda and u indices per ip, the
-            // side's contact-node lambda (C per node) and body-node u (3 per node) once;
-            // k_inpo_node: index + coefficient per (node, ip) entry, the node's C outputs
-            F.bytes_gamma += 48.0 * (double)nip + (double)F.nnc[s] * 8.0 * (F.C + 3);
-            F.bytes_inpo += 12.0 * (double)iq.size() + 8.0 * F.C * (double)nip + 8.0 * F.C * (double)F.nnc[s];
-            F.nptr[s].upload(ptr);
-            F.niq[s].upload(iq.empty() ? std::vector<int32_t>{0} : iq);
-            F.ncoef[s].upload(coef.empty() ? std::vector<double>{0.0} : coef);
+            if (!F.own[s]) continue;
+            D.M[s].upload(F.M[s]);
+            D.lam[s].upload(F.lam[s]);
+            D.u[s].upload(F.u[s]);
+            D.nptr[s].upload(F.nptr[s]);
+            D.niq[s].upload(F.niq[s]);
+            D.ncoef[s].upload(F.ncoef[s]);
         }
-        // per ip: the 3x3 basis, gamma written and the constant part read (k_gamma_ip); basis,
-        // gamma read and the traction written (k_traction_ip)
-        F.bytes_gamma += (double)nip * (72.0 + 16.0 * F.C);
-        F.bytes_inpo += (double)nip * ((F.C == 3 ? 72.0 : 0.0) + 16.0 * F.C);
-        H.fitfs.push_back(std::move(F));
+        H.fitfs.push_back(std::move(D));
     }
     // ---- interface operators over W (MCONTACT.h:2632-2636, 2671-2704)
+    H.fused = fused_update(mc, T, H.tune);
     {
-        // fused update when the penalty operators are exact multiples of the plain ones
-        // (entries agree to rounding: the penalty operators are accumulated with pen inside the
-        // basis products, e.g. off-diagonal T^T P T entries are rounding noise around 0)
-        auto proportional = [](const Csr& A, const Csr& B, double rho) {
-            if (A.nrow != B.nrow || A.ptr != B.ptr || A.col != B.col) return false;
-            double amax = 0.0;
-            for (double v : A.val) amax = std::max(amax, std::abs(v));
-            for (int64_t k = 0; k < A.nnz(); ++k)
-                if (std::abs(A.val[k] - rho * B.val[k]) > 1e-13 * amax) return false;
-            return true;
-        };
-        const char* env = std::getenv("DDPCA_MASS_FUSED");
-        bool fuse = !H.sides.empty() && (!env || std::atoi(env) != 0);
-        for (const auto& sd : H.sides) {
-            const Interface& itf = mc.searCont[sd.ts];
-            const double rho = itf.penN;
-            fuse = fuse && itf.penN == itf.penF && rho > 0.0 && proportional(itf.inteMass_pena[sd.s], itf.inteMass[sd.s], rho) &&
-                   proportional(itf.systTran_pena[sd.s], itf.systTran[sd.s], rho);
-        }
-        // (the fused update applies op_wv instead of op_aux / op_lam: their rows are built only
-        // for the sequential update)
-        Rows rg(H.G), ra(fuse ? 0 : H.R), rl(fuse ? 0 : H.R), rg1;
-        std::vector<int32_t> g1dst;
-        std::map<int64_t, int64_t> g1off;  // rank-local SELL interface -> its first row in rg1
-        std::vector<double> gc(H.G, 0.0);
-        for (const auto& sd : H.sides) {
-            const Interface& itf = mc.searCont[sd.ts];
-            const auto& I = itf_of(sd.ts);
-            const int s = (int)sd.s;
-            const double half = s == 0 ? 0.5 : -0.5;
-            const auto& Su = H.subs[sd.sub];
-            const int64_t lam0 = H.oS + H.R + sd.roff, aux0 = H.oS + sd.roff;
-            // gamma half: +-1/2 (inpoLagr lambda + pemaInpo_r u); side 0 adds -1/2 pema g
-            const Csr& Lg = itf.inpoLagr[s];
-            const Csr& Rg = itf.pemaInpo_r[s];
-            // a rank-local interface's side 1 sums its half in rows of its own (op_gamma1)
-            const bool own_rows1 = !itf.factored && s == 1 && !I.cross;
-            if (own_rows1 && !g1off.count(sd.ts)) {
-                g1off[sd.ts] = (int64_t)rg1.size();
-                for (int64_t i = 0; i < sd.mip; ++i) g1dst.push_back((int32_t)(I.goff + i));
-                rg1.resize(rg1.size() + sd.mip);
-            }
-            for (int64_t i = 0; i < sd.mip; ++i) {
-                if (!itf.factored) {  // factored interfaces: k_gamma_ip
-                    auto& row = own_rows1 ? rg1[g1off[sd.ts] + i] : rg[I.goff + i];
-                    for (int64_t k = Lg.ptr[i]; k < Lg.ptr[i + 1]; ++k) row.push_back({lam0 + Lg.col[k], half * Lg.val[k]});
-                    for (int64_t k = Rg.ptr[i]; k < Rg.ptr[i + 1]; ++k) row.push_back({Su.wcol(Rg.col[k], H.oH), half * Rg.val[k]});
-                }
-                if (s == 0) gc[I.goff + i] = -0.5 * (itf.pemaDiag[i] * itf.inpoNgap[i]);
-            }
-            if (fuse) continue;
-            // aux RHS: systTran_pena^T u + inteMass lambda + inteInpo gamma
-            const Csr tTp = csr::transpose(itf.systTran_pena[s]);
-            const Csr& M = itf.inteMass[s];
-            const Csr& Mp = itf.inteMass_pena[s];
-            const Csr& Ii = itf.inteInpo[s];
-            for (int64_t r = 0; r < sd.m; ++r) {
-                auto& a = ra[sd.roff + r];
-                auto& l = rl[sd.roff + r];
-                for (int64_t k = tTp.ptr[r]; k < tTp.ptr[r + 1]; ++k) {
-                    a.push_back({Su.wcol(tTp.col[k], H.oH), tTp.val[k]});
-                    l.push_back({Su.wcol(tTp.col[k], H.oH), tTp.val[k]});
-                }
-                for (int64_t k = M.ptr[r]; k < M.ptr[r + 1]; ++k) a.push_back({lam0 + M.col[k], M.val[k]});
-                for (int64_t k = Ii.ptr[r]; k < Ii.ptr[r + 1]; ++k) a.push_back({H.oG + I.goff + Ii.col[k], Ii.val[k]});
-                // lambda RHS: systTran_pena^T u - inteMass_pena aux
-                for (int64_t k = Mp.ptr[r]; k < Mp.ptr[r + 1]; ++k) l.push_back({aux0 + Mp.col[k], -Mp.val[k]});
-            }
-        }
-        H.op_gamma.build(rg);
-        if (!rg1.empty()) {
-            H.op_gamma1.build(rg1);
+        const AdmmOperators O = plan_operators(mc, T, H.fused);
+        H.op_gamma.upload(O.gamma);
+        if (O.has_gamma1) {
+            H.op_gamma1.upload(O.gamma1);
             H.gam1.alloc(H.op_gamma1.nrow);
-            H.gam1_dst.upload(g1dst);
+            H.gam1_dst.upload(O.gam1_dst);
         }
-        if (!fuse) {
-            H.op_aux.build(ra);
-            H.op_lam.build(rl);
+        if (!H.fused) {
+            H.op_aux.upload(O.aux);
+            H.op_lam.upload(O.lam);
         }
-        H.gcst.upload(gc);
-        std::vector<const Csr*> Ma, Ml;
-        std::vector<int64_t> ro;
-        for (auto& sd : H.sides) {
-            const Interface& itf = mc.searCont[sd.ts];
-            Ma.push_back(&itf.inteMass_pena[sd.s]);
-            Ml.push_back(&itf.inteMass[sd.s]);
-            ro.push_back(sd.roff);
-        }
-        // (built in the fused case too, where mb_wv solves instead: the iteration's check() and byte
-        // accounting walk all three batches, and the two cost 0.1 s at the headline size)
-        H.mb_aux.build(Ma, ro, H.R);
-        H.mb_lam.build(Ml, ro, H.R);
-        H.mb_aux.set_split(two_streams());
-        H.mb_lam.set_split(two_streams());
-        if (fuse) {
-            H.fused = true;
-            Rows rwv(2 * H.R);
-            std::vector<double> ri(std::max<int64_t>(H.R, 1), 0.0);
-            std::vector<const Csr*> M2;
-            std::vector<int64_t> ro2;
-            for (const auto& sd : H.sides) {
-                const Interface& itf = mc.searCont[sd.ts];
-                const auto& I = itf_of(sd.ts);
-                const auto& Su = H.subs[sd.sub];
-                const Csr tT = csr::transpose(itf.systTran[sd.s]);
-                const Csr& Ii = itf.inteInpo[sd.s];
-                for (int64_t r = 0; r < sd.m; ++r) {
-                    for (int64_t k = tT.ptr[r]; k < tT.ptr[r + 1]; ++k) rwv[sd.roff + r].push_back({Su.wcol(tT.col[k], H.oH), tT.val[k]});
-                    if (!itf.factored)  // factored interfaces: k_traction_ip + k_inpo_node
-                        for (int64_t k = Ii.ptr[r]; k < Ii.ptr[r + 1]; ++k)
-                            rwv[H.R + sd.roff + r].push_back({H.oG + I.goff + Ii.col[k], Ii.val[k]});
-                    ri[sd.roff + r] = 1.0 / itf.penN;
-                }
-                M2.push_back(&itf.inteMass[sd.s]);
-                ro2.push_back(sd.roff);
-            }
-            for (const auto& sd : H.sides) {
-                M2.push_back(&mc.searCont[sd.ts].inteMass[sd.s]);
-                ro2.push_back(H.R + sd.roff);
-            }
-            H.op_wv.build(rwv);
-            H.mb_wv.build(M2, ro2, 2 * H.R);
-            H.mb_wv.set_split(two_streams());
-            H.rinv.upload(ri);
-        }
-        if (std::getenv("DDPCA_VERBOSE"))
-            std::fprintf(stderr, "[ddpca] interface update: %s\n", H.fused ? "fused (one batched mass solve)" : "sequential");
+        H.gcst.upload(O.gcst);
     }
-    // ---- coupling rows of the body-balance RHS: sum over incident sides of
-    //      [systTran_pena | -systTran] on free dofs, solver dofs x W columns
+    // ---- surface-mass batches (built in the fused case too, where mb_wv solves instead: the
+    // iteration's check() and byte accounting walk all three batches, and the two cost 0.1 s at
+    // the headline size)
+    auto build_mass = [&](MassBatch& mb, int which) {
+        const MassList L = mass_list(mc, T, which);
+        mb.build(L.A, L.roff, L.nrow);
+    };
+    build_mass(H.mb_aux, 0);
+    build_mass(H.mb_lam, 1);
+    H.mb_aux.set_split(two_streams());
+    H.mb_lam.set_split(two_streams());
+    if (H.fused) {
+        const AdmmFused F = plan_fused(mc, T);
+        H.op_wv.upload(F.wv);
+        build_mass(H.mb_wv, 2);
+        H.mb_wv.set_split(two_streams());
+        H.rinv.upload(F.rinv);
+    }
+    if (H.tune.verbose)
+        std::fprintf(stderr, "[ddpca] interface update: %s\n", H.fused ? "fused (one batched mass solve)" : "sequential");
+    // ---- coupling rows of the body-balance RHS
+    double coupling_bytes = 0.0;
     {
-        std::map<int64_t, std::vector<std::pair<int32_t, double>>> rowmap;
-        for (size_t si = 0; si < H.subs.size(); ++si) {
-            const auto& S = H.subs[si];
-            const MULTIGRID& g = mc.multGrid[S.tv];
-            for (int64_t ts = 0; ts < H.nint; ++ts) {
-                const Interface& itf = mc.searCont[ts];
-                for (int s = 0; s < 2; ++s) {
-                    if (itf.body[s] != S.tv) continue;
-                    const auto& sd = H.sides[side_of.at({ts, s})];
-                    const Csr& Tp = itf.systTran_pena[s];
-                    const Csr& T = itf.systTran[s];
-                    const int64_t n3 = 3 * S.nn;
-                    for (int64_t r = 0; r < Tp.nrow; ++r) {
-                        // only the rows the interface actually couples (surface rows)
-                        if (Tp.ptr[r] == Tp.ptr[r + 1] && T.ptr[r] == T.ptr[r + 1]) continue;
-                        // a hanging-level row reaches the free dofs through prolOper[maxiLeve]^T
-                        // (ADDITIONAL_FORCE, MULTIGRID.h:1257-1261)
-                        std::vector<std::pair<int64_t, double>> tgt;
-                        if (r < n3) {
-                            tgt.push_back({r, 1.0});
-                        } else {
-                            const Csr& Hp = g.hangProl;
-                            for (int64_t k = Hp.ptr[r - n3]; k < Hp.ptr[r - n3 + 1]; ++k) tgt.push_back({Hp.col[k], Hp.val[k]});
-                        }
-                        for (const auto& [d, w] : tgt) {
-                            if (!g.consFlag[d] || w == 0.0) continue;
-                            auto& row = rowmap[H.mg->fine_dof((int)si, d)];  // added into the solver RHS
-                            for (int64_t k = Tp.ptr[r]; k < Tp.ptr[r + 1]; ++k)
-                                row.push_back({(int32_t)(H.oS + sd.roff + Tp.col[k]), w * Tp.val[k]});
-                            for (int64_t k = T.ptr[r]; k < T.ptr[r + 1]; ++k)
-                                row.push_back({(int32_t)(H.oS + H.R + sd.roff + T.col[k]), -w * T.val[k]});
-                        }
-                    }
-                }
-            }
-        }
-        std::vector<int32_t> crow;
-        std::vector<int64_t> cptr{0};
-        std::vector<int32_t> ccol;
-        std::vector<double> cval;
-        for (auto& kv : rowmap) {
-            crow.push_back((int32_t)kv.first);
-            // merge duplicate columns (hanging rows folded onto the same free dof)
-            std::stable_sort(kv.second.begin(), kv.second.end(),
-                             [](const auto& a, const auto& b) { return a.first < b.first; });
-            for (size_t e = 0; e < kv.second.size();) {
-                size_t f = e;
-                double v = 0.0;
-                for (; f < kv.second.size() && kv.second[f].first == kv.second[e].first; ++f) v += kv.second[f].second;
-                ccol.push_back(kv.second[e].first);
-                cval.push_back(v);
-                e = f;
-            }
-            cptr.push_back((int64_t)ccol.size());
-        }
-        H.ncrow = (int64_t)crow.size();
-        {
-            // k_cpl: entries, the row's target index and pointer, b read + written, W's aux and
-            // lambda entries once
-            std::vector<int32_t> uc(ccol);
-            std::sort(uc.begin(), uc.end());
-            const double uniq = (double)(std::unique(uc.begin(), uc.end()) - uc.begin());
-            H.bytes_rhs += 12.0 * (double)ccol.size() + 28.0 * (double)H.ncrow + 8.0 * uniq;
-        }
-        H.crow.upload(crow);
-        H.cptr.upload(cptr);
-        H.ccol.upload(ccol);
-        H.cval.upload(cval);
+        const CouplingPlan K = plan_coupling(mc, T, V);
+        H.ncrow = (int64_t)K.crow.size();
+        coupling_bytes = K.bytes;
+        H.crow.upload(K.crow);
+        H.cptr.upload(K.cptr);
+        H.ccol.upload(K.ccol);
+        H.cval.upload(K.cval);
     }
-    // ---- hanging-level values over u: one SELL-64 product (rows of prolOper[maxiLeve])
-    if (H.NH) {
-        Rows rh(H.NH);
-        for (const auto& S : H.subs) {
-            const Csr& Hp = mc.multGrid[S.tv].hangProl;
-            for (int64_t r = 0; r < S.nh; ++r)
-                for (int64_t k = Hp.ptr[r]; k < Hp.ptr[r + 1]; ++k) rh[S.hoff + r].push_back({S.wcol(Hp.col[k], H.oH), Hp.val[k]});
-        }
-        H.op_hang.build(rh);
-    }
-    // per-ADMM-iteration byte model of the launches outside the PCG, mass CG and coarse space
+    // ---- hanging-level values over u
+    if (H.NH) H.op_hang.upload(plan_hanging(mc, T));
+    // ---- per-ADMM-iteration byte model
     {
-        double nu = 0.0, rows = 0.0;
-        for (auto& S : H.subs) nu += 3.0 * (double)S.nn + (double)S.nh;
-        for (auto& sd : H.sides) rows += (double)sd.m;
-        double fine_nodes = 0.0;
-        for (auto& S : H.subs) fine_nodes += (double)S.nn;
-        // consForc copied into b (16 B per dof), k_outp (x, presc read, u written, mask, node map:
-        // 77 B per node), the hanging rows
-        H.bytes_rhs += 16.0 * 3.0 * fine_nodes + 77.0 * fine_nodes + (H.NH ? H.op_hang.bytes : 0.0);
-        // interface: gamma (stored rows + the constant), factored per-ip kernels, projection,
-        // the aux / lambda right-hand sides, the fused update (or the lambda add)
-        H.bytes_iface += H.op_gamma.nch ? H.op_gamma.bytes + 8.0 * (double)H.op_gamma.nrow : 0.0;
-        // side-1 halves of rank-local interfaces: their rows, then gamma read + written and the half read
-        H.bytes_iface += H.op_gamma1.nch ? H.op_gamma1.bytes + 28.0 * (double)H.gam1_dst.n : 0.0;
-        for (auto& F : H.fitfs) H.bytes_iface += F.bytes_gamma + (H.fused ? F.bytes_inpo : 0.0);
-        for (auto& I : H.itfs)
-            if (I.mine) H.bytes_iface += (double)(I.mip / I.comp) * (16.0 * I.comp + 4.0) + (I.cross ? 24.0 * I.mip : 0.0);
-        if (H.fused) H.bytes_iface += H.op_wv.bytes + 56.0 * rows;
-        else if (!H.sides.empty()) H.bytes_iface += H.op_aux.bytes + H.op_lam.bytes + 24.0 * rows;
-        // MONITOR: snapshots of u and [aux, lambda] (read + written), the pair norms (16 B per entry)
-        H.bytes_moni = 16.0 * (nu + 2.0 * rows) + 16.0 * (nu + 2.0 * rows);
+        std::vector<const FactItfShape*> fact;
+        for (const auto& F : H.fitfs) fact.push_back(&F);
+        const AdmmBytes B = admm_byte_model(T, H.fused, coupling_bytes, H.op_hang, H.op_gamma, H.op_gamma1, (int64_t)H.gam1_dst.n,
+                                            fact, H.op_aux, H.op_lam, H.op_wv);
+        H.bytes_rhs = B.rhs;
+        H.bytes_iface = B.iface;
+        H.bytes_moni = B.moni;
     }
     // monitor norms [2 nsub u | 8 nint aux, lambda | 2 nsub hanging-level parts of u]
     const int64_t nmon = 4 * H.nsub + 8 * H.nint;
@@ -1149,174 +792,14 @@ void build(ddpca_mcontact& H, Problem& P) {
     H.moni_host.assign(nmon, 0.0);
     H.moniReco.assign(H.nsub + 4 * H.nint, std::vector<double>(10, 0.0));
     DDPCA_HIP(hipStreamSynchronize(H.main));
-}
-
-// ---- DOUBLE_M_1 (MCONTACT.h:2303-2341): level l of the coarse hierarchy (l = Lc = max doleMcsc is
-// globCoup_1 itself) holds level max(0, doleMcsc[tv] - (Lc - l)) of every subdomain; the transfer
-// below it is each subdomain's realProl at that level (identity where a subdomain has reached its
-// level 0), and the level operators are Galerkin products.  Nodes are numbered so that every level
-// is a prefix of the next (the layout MgpisDevice takes): level l = level l-1's nodes, then the new
-// nodes of every subdomain in order.  Needs every subdomain's coarse rows on this rank.
-void plan_coarse_mg(const MCONTACT& mc, CoarseDev& C) {
-    const CoarseSpace& cs = mc.coarse;
-    const int64_t nsub = (int64_t)mc.multGrid.size(), n = C.n;
-    CoarseDev::MgPlan& PL = C.plan;
-    const int64_t Lc = *std::max_element(mc.doleMcsc.begin(), mc.doleMcsc.end());
-    auto lev = [&](int64_t tv, int64_t l) { return std::max<int64_t>(0, mc.doleMcsc[tv] - (Lc - l)); };
-    std::vector<std::vector<std::vector<int64_t>>> gid(Lc + 1, std::vector<std::vector<int64_t>>(nsub));
-    // LATIN (DOUBLE_M, MCONTACT.h:1538-1670): the coarse contact unknowns of every interface are a
-    // group of their own -- at level Lc the level-doleMcsc nodes coarNode[ts] of contBody[ts][0],
-    // one level down the columns its scalProl rows touch (ficoCotr), comp unknowns per node
-    // (the node's first dof for frictionless contact).  The sets need not be nested: a node of
-    // level l - 1 that level l does not carry (stacked bodies: BLOCK) keeps the prefix layout as a
-    // masked copy on level l and above (per-level dof flags, SubdomainOps::dof_free_lev) -- the
-    // masked transfer C_l P C_{l-1}^T then is the reference's ficoCotr
-    const int64_t nint = cs.latin ? (int64_t)mc.searCont.size() : 0;
-    if (cs.latin && (int64_t)cs.coarNode.size() != nint)
-        throw ApiError(DDPCA_EINVAL, "DOUBLE_M for the LATIN coarse space needs the coarse contact nodes (coarNode)");
-    std::vector<std::vector<std::vector<int64_t>>> cset(Lc + 1, std::vector<std::vector<int64_t>>(nint));
-    for (int64_t ts = 0; ts < nint; ++ts) {
-        const int64_t b0 = mc.searCont[ts].body[0];
-        const MULTIGRID& g = mc.multGrid[b0];
-        cset[Lc][ts] = cs.coarNode[ts];
-        for (int64_t l = Lc; l >= 1; --l) {
-            const int64_t fl = mc.doleMcsc[b0] - (Lc - l);  // the group's node level at l
-            if (fl - 1 < 0) {
-                cset[l - 1][ts] = cset[l][ts];
-                continue;
-            }
-            const Stencil& Sp = g.scalProl[fl - 1];  // scalar, no rotations (MCONTACT.h:1553)
-            if (!Sp.bent.empty())
-                throw ApiError(DDPCA_EINVAL, "LATIN DOUBLE_M: ficoCotr needs the scalar scalProl (a caller's rotated realProl has none)");
-            std::vector<int64_t> cols;
-            for (int64_t f : cset[l][ts])
-                for (int64_t k = Sp.ptr[f]; k < Sp.ptr[f + 1]; ++k) cols.push_back(Sp.col[k]);
-            std::sort(cols.begin(), cols.end());
-            cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-            cset[l - 1][ts] = cols;
-        }
-    }
-    std::vector<std::unordered_map<int64_t, int64_t>> cg(nint);  // (interface, node) -> global node
-    std::vector<int64_t> nglob(Lc + 1, 0);
-    for (int64_t l = 0; l <= Lc; ++l) {
-        int64_t cnt = l ? nglob[l - 1] : 0;
-        for (int64_t tv = 0; tv < nsub; ++tv) {
-            auto& v = gid[l][tv];
-            v.resize(mc.multGrid[tv].leveCount[lev(tv, l)]);
-            int64_t keep = 0;
-            if (l) {
-                keep = (int64_t)gid[l - 1][tv].size();
-                std::copy(gid[l - 1][tv].begin(), gid[l - 1][tv].end(), v.begin());
-            }
-            for (int64_t j = keep; j < (int64_t)v.size(); ++j) v[j] = cnt++;
-        }
-        for (int64_t ts = 0; ts < nint; ++ts)
-            for (int64_t node : cset[l][ts])
-                if (cg[ts].emplace(node, cnt).second) ++cnt;
-        nglob[l] = cnt;
-    }
-    std::vector<Stencil> S(Lc);
-    for (int64_t l = 1; l <= Lc; ++l) {
-        std::vector<std::vector<std::pair<int32_t, double>>> rows(nglob[l]);
-        for (int64_t i = 0; i < nglob[l - 1]; ++i) rows[i].push_back({(int32_t)i, 1.0});
-        std::vector<std::vector<std::array<double, 9>>> rblk(nglob[l]);  // block entries, parallel to rows (NaN-free marker below)
-        for (int64_t tv = 0; tv < nsub; ++tv) {
-            if (lev(tv, l) == lev(tv, l - 1)) continue;  // identity (MCONTACT.h:2325-2331)
-            // the subdomain's realProl at that level (MCONTACT.h:1632, 2316): prolOper's rotation
-            // blocks as block entries (a caller's operator-level stencil carries them in scalProl)
-            const MULTIGRID& g = mc.multGrid[tv];
-            const Stencil& Sp = g.prolOper.empty() ? g.scalProl[lev(tv, l - 1)] : g.prolOper[lev(tv, l - 1)];
-            std::vector<int64_t> bo(Sp.col.size(), -1);
-            for (size_t q = 0; q < Sp.bent.size(); ++q) bo[Sp.bent[q]] = (int64_t)q;
-            for (int64_t j = (int64_t)gid[l - 1][tv].size(); j < (int64_t)gid[l][tv].size(); ++j)
-                for (int64_t k = Sp.ptr[j]; k < Sp.ptr[j + 1]; ++k) {
-                    const int64_t r = gid[l][tv][j];
-                    rows[r].push_back({(int32_t)gid[l - 1][tv][Sp.col[k]], Sp.w[k]});
-                    std::array<double, 9> b;
-                    if (bo[k] >= 0) std::copy(&Sp.bval[9 * bo[k]], &Sp.bval[9 * bo[k]] + 9, b.begin());
-                    else b[0] = std::numeric_limits<double>::quiet_NaN();  // scalar entry
-                    rblk[r].resize(rows[r].size());
-                    rblk[r].back() = b;
-                }
-        }
-        for (int64_t ts = 0; ts < nint; ++ts) {  // ficoCotr rows of the nodes new on level l
-            const int64_t b0 = mc.searCont[ts].body[0];
-            const int64_t fl = mc.doleMcsc[b0] - (Lc - l);
-            if (fl - 1 < 0) continue;
-            const Stencil& Sp = mc.multGrid[b0].scalProl[fl - 1];
-            for (int64_t f : cset[l][ts]) {
-                if (std::binary_search(cset[l - 1][ts].begin(), cset[l - 1][ts].end(), f)) continue;  // coarse copy
-                auto& row = rows[cg[ts].at(f)];
-                for (int64_t k = Sp.ptr[f]; k < Sp.ptr[f + 1]; ++k) row.push_back({(int32_t)cg[ts].at(Sp.col[k]), Sp.w[k]});
-            }
-        }
-        Stencil& T = S[l - 1];
-        T.nf = nglob[l];
-        T.nc = nglob[l - 1];
-        T.ptr.assign(1, 0);
-        for (int64_t r = 0; r < nglob[l]; ++r) {
-            for (size_t q = 0; q < rows[r].size(); ++q) {
-                const bool blk = q < rblk[r].size() && !std::isnan(rblk[r][q][0]);
-                if (blk) {
-                    T.bent.push_back((int64_t)T.col.size());
-                    T.bval.insert(T.bval.end(), rblk[r][q].begin(), rblk[r][q].end());
-                }
-                T.col.push_back(rows[r][q].first);
-                T.w.push_back(blk ? 0.0 : rows[r][q].second);
-            }
-            T.ptr.push_back((int64_t)T.col.size());
-        }
-    }
-    // globCoup(_1) rows: subdomain tv's level-doleMcsc free dofs in increasing order (consOper),
-    // then (LATIN) every interface's coarse contact unknowns, comp per node
-    std::vector<int32_t> fdg(n);
-    for (int64_t tv = 0; tv < nsub; ++tv) {
-        const MULTIGRID& g = mc.multGrid[tv];
-        int64_t r = cs.baseReco[tv];
-        for (int64_t dof = 0; dof < 3 * g.leveCount[mc.doleMcsc[tv]]; ++dof)
-            if (g.consFlag[dof]) fdg[r++] = (int32_t)(3 * gid[Lc][tv][dof / 3] + dof % 3);
-        if (r != cs.baseReco[tv + 1]) throw ApiError(DDPCA_EINVAL, "DOUBLE_M: baseReco does not match the free dofs");
-    }
-    {
-        int64_t r = cs.baseReco[nsub];
-        for (int64_t ts = 0; ts < nint; ++ts) {
-            const int comp = mc.searCont[ts].comp();
-            for (int64_t node : cset[Lc][ts])
-                for (int j = 0; j < comp; ++j) fdg[r++] = (int32_t)(3 * cg[ts].at(node) + j);
-        }
-        if (r != n) throw ApiError(DDPCA_EINVAL, "DOUBLE_M: coarse contact unknowns do not match the coarse rows");
-    }
-    // per-level dof flags: a subdomain node's dofs as its consOper (the prefix of its flags), a
-    // contact unknown's comp dofs free on the levels that carry it, its masked copies none
-    std::vector<std::vector<uint8_t>> flev(Lc + 1);
-    for (int64_t l = 0; l <= Lc; ++l) {
-        auto& f = flev[l];
-        f.assign(3 * nglob[l], 0);
-        for (int64_t tv = 0; tv < nsub; ++tv) {
-            const MULTIGRID& g = mc.multGrid[tv];
-            for (size_t j = 0; j < gid[l][tv].size(); ++j)
-                for (int a = 0; a < 3; ++a) f[3 * gid[l][tv][j] + a] = g.consFlag[3 * j + a];
-        }
-        for (int64_t ts = 0; ts < nint; ++ts) {
-            const int comp = mc.searCont[ts].comp();
-            for (int64_t node : cset[l][ts])
-                for (int j = 0; j < comp; ++j) f[3 * cg[ts].at(node) + j] = 1;
-        }
-    }
-    for (int32_t d : fdg)
-        if (!flev[Lc][d]) throw ApiError(DDPCA_EINVAL, "DOUBLE_M: a coarse row on a constrained dof");
-    PL.nglob = std::move(nglob);
-    PL.S = std::move(S);
-    PL.fdg = std::move(fdg);
-    PL.flev = std::move(flev);
-    PL.latin = cs.latin;
+    return T;
 }
 
 // The coarse MGPIS from the plan and the whole coarse operator A (globCoup_1 / globCoup):
 // K[Lc] = A on the hierarchy's fine level, the levels below Galerkin products (MCONTACT.h:
 // 1664-1665, 2337-2338)
 void finish_coarse_mg(ddpca_mcontact& H, CoarseDev& C, const Csr& A) {
-    CoarseDev::MgPlan& PL = C.plan;
+    MgPlan& PL = C.plan;
     const int64_t n = C.n, Lc = (int64_t)PL.nglob.size() - 1;
     if (A.nrow != n || A.ncol != n) throw ApiError(DDPCA_EINVAL, "DOUBLE_M coarse solve: the whole coarse operator is needed");
     std::vector<Bsr3> K(Lc + 1);
@@ -1335,15 +818,15 @@ void finish_coarse_mg(ddpca_mcontact& H, CoarseDev& C, const Csr& A) {
     C.cown.upload(own.empty() ? std::vector<int32_t>{0} : own);
     DDPCA_HIP(hipEventCreateWithFlags(&C.ev_in, hipEventDisableTiming));
     DDPCA_HIP(hipEventCreateWithFlags(&C.ev_out, hipEventDisableTiming));
-    if (std::getenv("DDPCA_VERBOSE"))
+    if (H.tune.verbose)
         std::fprintf(stderr, "[ddpca] DOUBLE_M%s coarse solve: %ld rows, %ld levels%s\n", PL.latin ? "" : "_1", (long)n,
                      (long)(Lc + 1), C.mg_gather ? " (operator gathered from every rank)" : "");
-    CoarseDev::MgPlan().swap_into(PL);
+    PL = MgPlan();
 }
 
-// ---- coarse space: device operands from the host MULTISCALE_1 output
-void build_coarse(ddpca_mcontact& H, Problem& P) {
-    MCONTACT& mc = P.mc;
+// ---- coarse space: device operands from the host MULTISCALE_1 output (T: build's tables)
+void build_coarse(ddpca_mcontact& H, const Problem& P, const AdmmTables& T) {
+    const MCONTACT& mc = P.mc;
     const CoarseSpace& cs = mc.coarse;
     CoarseDev& C = H.cs;
     if (!(mc.muscSett & 3)) return;
@@ -1351,143 +834,21 @@ void build_coarse(ddpca_mcontact& H, Problem& P) {
     C.on = true;
     C.n = cs.n;
     const int64_t n = C.n;
-    std::vector<int64_t> xoff(H.subs.size());
-    for (size_t i = 0; i < H.subs.size(); ++i) {
-        const int64_t tv = H.subs[i].tv;
-        if (!cs.built[tv]) throw ApiError(DDPCA_ESTATE, "coarse rows of an owned subdomain were not built");
-        xoff[i] = (int64_t)C.own_rows.size();
-        for (int64_t r = cs.baseReco[tv]; r < cs.baseReco[tv + 1]; ++r) C.own_rows.push_back(r);
-    }
+    // ---- the right-hand side in per-source slots (plan_coarse_rhs has the why)
+    CoarseRhsPlan R = plan_coarse_rhs(mc, T);
+    C.own_rows = R.own_rows;
     C.nown = (int64_t)C.own_rows.size();
-    // ---- the right-hand side in per-source slots.  Row r of the coarse right-hand side sums
-    // contributions of several subdomains (its own u and lambda, its interface mates' through
-    // globTran_1 / globTran_S; LATIN's contact rows both bodies of the interface), and every source
-    // subdomain lives on exactly one rank.  Summing the row over this rank's W columns and then
-    // all-reducing across ranks would round differently for every rank layout; instead every row
-    // has one slot per structurally possible source (the same layout on every rank: itself and its
-    // interface mates, for LATIN's contact rows both bodies), each slot is summed in a fixed,
-    // layout-independent order by its source's owner (the other ranks contribute exact zeros to
-    // it), the slots are all-reduced, and k_slot_sum adds a row's slots in ascending source order.
-    // The coarse right-hand side -- and so the whole trajectory -- is then the same bits on any
-    // number of ranks (tests/test_mcontact_gpu.py: resuMoni rows of the multi-rank runs).
-    const int64_t nsg = (int64_t)cs.baseReco.size() - 1, nbase = cs.baseReco.back();
-    std::vector<std::vector<int64_t>> srcs(n);
-    {
-        std::vector<std::vector<int64_t>> nbr(nsg);
-        std::vector<int64_t> bodies;
-        for (int64_t tv = 0; tv < nsg; ++tv) nbr[tv].push_back(tv);
-        for (const auto& itf : mc.searCont) {
-            nbr[itf.body[0]].push_back(itf.body[1]);
-            nbr[itf.body[1]].push_back(itf.body[0]);
-            bodies.push_back(itf.body[0]);
-            bodies.push_back(itf.body[1]);
-        }
-        auto uniq = [](std::vector<int64_t>& v) {
-            std::sort(v.begin(), v.end());
-            v.erase(std::unique(v.begin(), v.end()), v.end());
-        };
-        for (auto& v : nbr) uniq(v);
-        uniq(bodies);
-        for (int64_t tv = 0; tv < nsg; ++tv)
-            for (int64_t r = cs.baseReco[tv]; r < cs.baseReco[tv + 1]; ++r) srcs[r] = nbr[tv];
-        // LATIN's coarse contact unknowns: rows of interface ts take its two bodies when the
-        // unknowns are known per interface (coarNode), else every body of an interface
-        int64_t known = 0;
-        for (int64_t ts = 0; ts < (int64_t)cs.coarNode.size(); ++ts)
-            known += mc.searCont[ts].comp() * (int64_t)cs.coarNode[ts].size();
-        if (cs.coarNode.size() == mc.searCont.size() && nbase + known == n) {
-            int64_t r = nbase;
-            for (int64_t ts = 0; ts < (int64_t)cs.coarNode.size(); ++ts) {
-                std::vector<int64_t> b{mc.searCont[ts].body[0], mc.searCont[ts].body[1]};
-                uniq(b);
-                for (int64_t q = 0; q < mc.searCont[ts].comp() * (int64_t)cs.coarNode[ts].size(); ++q) srcs[r++] = b;
-            }
-        } else {
-            for (int64_t r = nbase; r < n; ++r) srcs[r] = bodies;
-        }
-    }
-    std::vector<int64_t> sptr(n + 1, 0);
-    for (int64_t r = 0; r < n; ++r) sptr[r + 1] = sptr[r] + (int64_t)srcs[r].size();
-    C.nslot = sptr[n];
-    auto slot_of = [&](int64_t r, int64_t tv) {
-        const auto& v = srcs[r];
-        const auto it = std::lower_bound(v.begin(), v.end(), tv);
-        if (it == v.end() || *it != tv)
-            throw ApiError(DDPCA_EINVAL, "coarse right-hand side: row " + std::to_string(r) + " has an entry of subdomain " +
-                                             std::to_string(tv) + ", which is not on the row's interface graph");
-        return sptr[r] + (int64_t)(it - v.begin());
-    };
-    // RHS entries over W: + globTran_1 (owned sides, lambda columns), - interface part of
-    // globTran_D_1 (owned subdomains, u columns); LATIN + globTran lambda - globTran_pena aux +
-    // globTran_D u.  Sort key inside a slot: (segment, global side, column in the source's own
-    // numbering) -- none of it depends on where the source's columns sit in this rank's W
-    struct Ent {
-        int64_t seg, side, lcol;
-        int32_t wc;
-        double v;
-        bool operator<(const Ent& o) const {
-            return seg != o.seg ? seg < o.seg : side != o.side ? side < o.side : lcol < o.lcol;
-        }
-    };
-    std::vector<std::vector<Ent>> ents(C.nslot);
-    auto put = [&](int64_t r, int64_t tv, Ent e) { ents[slot_of(r, tv)].push_back(e); };
-    for (const auto& sd : H.sides) {
-        const int64_t lam0 = H.oS + H.R + sd.roff, aux0 = H.oS + sd.roff, sg = 2 * sd.ts + sd.s;
-        const auto& Su = H.subs[sd.sub];
-        auto add_rows = [&](const Csr& T, int64_t seg, int64_t c0, double sgn, bool ucol) {
-            for (int64_t r = 0; r < T.nrow; ++r)
-                for (int64_t k = T.ptr[r]; k < T.ptr[r + 1]; ++k)
-                    put(r, sd.tv, Ent{seg, sg, T.col[k], (int32_t)(ucol ? Su.wcol(T.col[k], H.oH) : c0 + T.col[k]), sgn * T.val[k]});
-        };
-        if (cs.latin) {  // (MCONTACT.h:2540-2548)
-            add_rows(cs.globTran_D_L[sd.ts][sd.s], 1, 0, 1.0, true);
-            add_rows(cs.globTran_pena_L[sd.ts][sd.s], 2, aux0, -1.0, false);
-            add_rows(cs.globTran_L[sd.ts][sd.s], 3, lam0, 1.0, false);
-        } else {
-            add_rows(cs.globTran_1[sd.ts][sd.s], 3, lam0, 1.0, false);
-        }
-    }
-    for (size_t i = 0; i < H.subs.size() && !cs.latin; ++i) {
-        // factored: the interface part (the stiffness part is the SpMV + restriction chain);
-        // assembled: the caller's whole globTran_D_1
-        const Csr& T = cs.assembled ? cs.globTran_D_full[H.subs[i].tv] : cs.globTran_S[H.subs[i].tv];
-        const auto& Su = H.subs[i];
-        for (int64_t r = 0; r < T.nrow; ++r)
-            for (int64_t k = T.ptr[r]; k < T.ptr[r + 1]; ++k)
-                put(r, Su.tv, Ent{0, 0, T.col[k], (int32_t)Su.wcol(T.col[k], H.oH), -T.val[k]});
-    }
-    {
-        std::vector<int64_t> ptr(C.nslot + 1, 0);
-        std::vector<int32_t> col;
-        std::vector<double> val;
-        for (int64_t q = 0; q < C.nslot; ++q) {
-            auto& e = ents[q];
-            std::stable_sort(e.begin(), e.end());
-            for (const auto& x : e) {
-                col.push_back(x.wc);
-                val.push_back(x.v);
-            }
-            ptr[q + 1] = (int64_t)col.size();
-            std::vector<Ent>().swap(e);
-        }
-        C.rptr.upload(ptr);
-        C.rcol.upload(col.empty() ? std::vector<int32_t>{0} : col);
-        C.rval.upload(val.empty() ? std::vector<double>{0.0} : val);
-        C.sptr.upload(sptr);
-        // right-hand side CSR over W: entries, each distinct W entry once, f0 read and the slot
-        // written; the slot sum reads the slots and row pointers and writes g
-        std::vector<int32_t> uc(col);
-        std::sort(uc.begin(), uc.end());
-        const double uniq = (double)(std::unique(uc.begin(), uc.end()) - uc.begin());
-        C.bytes_iter = 12.0 * (double)col.size() + 8.0 * uniq + 16.0 * (double)C.nslot +
-                       8.0 * (double)C.nslot + 16.0 * (double)n;
-    }
-    // globForc_1 enters the slot of the row's own subdomain (the rank that owns the row)
-    std::vector<double> f0(std::max<int64_t>(C.nslot, 1), 0.0);
-    for (size_t i = 0; i < H.subs.size(); ++i)
-        for (int64_t r = cs.baseReco[H.subs[i].tv]; r < cs.baseReco[H.subs[i].tv + 1]; ++r)
-            f0[slot_of(r, H.subs[i].tv)] = cs.globForc_1[r];
-    C.f0.upload(f0);
+    C.nslot = R.nslot;
+    C.bytes_iter = R.bytes;
+    C.rptr.upload(R.rptr);
+    C.rcol.upload(R.rcol);
+    C.rval.upload(R.rval);
+    C.sptr.upload(R.slots.sptr);
+    C.f0.upload(R.f0);
+    std::vector<int64_t>().swap(R.rptr);  // (the slots and xoff stay for the prolongation tables)
+    std::vector<int32_t>().swap(R.rcol);
+    std::vector<double>().swap(R.rval);
+    std::vector<double>().swap(R.f0);
     if (!cs.latin && H.nranks == 1) {
         C.apps_A = cs.globCoup_1;
         C.apps_f.assign(cs.globForc_1.begin(), cs.globForc_1.end());
@@ -1495,207 +856,56 @@ void build_coarse(ddpca_mcontact& H, Problem& P) {
     C.gs.alloc(std::max<int64_t>(C.nslot, 1));
     C.g.alloc(std::max<int64_t>(n, 1));
     C.xc.alloc(std::max<int64_t>(C.nown, 1));
-    // the reference solves globCoup_1 directly below DIRE_MAXI = 120000 rows and with its DOUBLE_M_1
-    // MGPIS above (PREP.h:69, MCONTACT.h:1857-1865); DDPCA_COARSE_MG_MIN moves the switch (tests).
-    // The direct solve here is a dense explicit inverse, n^2 8 B on every rank and streamed by the
-    // GEMV every ADMM iteration, so it is also bounded by memory: above DDPCA_COARSE_DENSE_MB
-    // (default 1024 MiB, n ~ 11,600 rows) the multigrid solve takes over below DIRE_MAXI too --
-    // where the inverse would cost ~0.2 ms of HBM streaming per iteration and grow as n^2
-    const char* mg_env = std::getenv("DDPCA_COARSE_MG_MIN");
-    const char* dense_env = std::getenv("DDPCA_COARSE_DENSE_MB");
-    const double dense_max = (dense_env ? std::atof(dense_env) : 1024.0) * 1048576.0;
-    C.dense_bytes = 8.0 * (double)n * (double)n;
-    // LATIN: DOUBLE_M (MCONTACT.h:1236) on the coarse contact nodes (the host MULTISCALE's, or the
-    // caller's through ddpca_problem_set_coarse_nodes)
-    if (cs.latin && cs.coarNode.empty() && (n >= (mg_env ? std::atoll(mg_env) : 120000) || C.dense_bytes > dense_max))
-        throw ApiError(DDPCA_EINVAL, "LATIN coarse space past the dense solve's limits needs its coarse contact nodes "
-                                     "(ddpca_problem_set_coarse_nodes) for DOUBLE_M");
-    const bool by_rows = n >= (mg_env ? std::atoll(mg_env) : 120000);
-    const bool by_budget = C.dense_bytes > dense_max;  // the same decision on every rank: n is global
-    C.mg = by_rows || by_budget;
+    // ---- the solve: dense inverse or DOUBLE_M(_1) (coarse_solve_choice)
+    const CoarseSolveChoice S = coarse_solve_choice(cs, C.nown, H.nranks, H.tune);
+    C.dense_bytes = S.dense_bytes;
+    C.mg = S.mg;
+    C.mg_gather = S.mg_gather;
     C.latin = cs.latin;
-    // the multigrid hierarchy needs the whole coarse operator: a caller's full operator or a
-    // single-rank build has it; a rank-local build gathers it from every rank once the transport
-    // exists (coarse_invert)
-    bool full = !cs.rank_local;
-    for (int64_t tv = 0; tv < (int64_t)cs.built.size(); ++tv) full = full && cs.built[tv];
-    if (C.mg && !full && H.nranks == 1)
-        throw ApiError(DDPCA_ESTATE, "DOUBLE_M coarse solve: a single rank without every subdomain's coarse rows");
-    C.mg_gather = C.mg && !full;
     if (C.mg && H.mg) {
-        plan_coarse_mg(mc, C);
+        C.plan = plan_coarse_mg(mc, n);
         if (!C.mg_gather) finish_coarse_mg(H, C, cs.globCoup_1);
         else C.gathered_rows = cs.globCoup_1;  // this rank's rows (its share of the contact rows)
     }
-    // coarse solve: the owned rows of the dense inverse against g, or (DOUBLE_M) g scattered into
-    // the coarse MGPIS and its owned rows gathered back (its PCG is counted by its own model)
-    C.bytes_iter += C.mg ? 20.0 * (double)n + 24.0 * (double)C.nown
-                         : 8.0 * (double)C.nown * (double)n + 8.0 * (double)n + 8.0 * (double)C.nown;
-    if (!C.mg) {
-        // dense rows of globCoup_1 (inverted once every rank holds all rows)
-        C.dense.assign((size_t)n * n, 0.0);
-        std::vector<int64_t> fill_rows = C.own_rows;
-        // the coarse contact unknowns' rows: a caller's full operator is filled by rank 0 only; a
-        // rank-local host build holds each rank's share (the all-reduce sums them)
-        if (cs.latin && (cs.rank_local || H.rank == 0))
-            for (int64_t r = cs.baseReco.back(); r < n; ++r) fill_rows.push_back(r);
-        for (int64_t r : fill_rows)
-            for (int64_t k = cs.globCoup_1.ptr[r]; k < cs.globCoup_1.ptr[r + 1]; ++k)
-                C.dense[(size_t)r * n + cs.globCoup_1.col[k]] = cs.globCoup_1.val[k];
-    }
+    C.bytes_iter += S.bytes;
+    // dense rows of globCoup_1 (inverted once every rank holds all rows)
+    if (!C.mg) C.dense = coarse_dense_rows(cs, C.own_rows, H.rank);
     if (!H.mg) return;
+    // ---- u += accuProl x_c, and (factored) the stiffness part's gather groups
     C.assembled = cs.assembled;
     if (cs.assembled) {
-        std::vector<int64_t> ptr{0};
-        std::vector<int32_t> col, tgt, cd;
-        std::vector<double> val;
-        for (size_t i = 0; i < H.subs.size(); ++i) {
-            const int64_t tv = H.subs[i].tv;
-            const MULTIGRID& g = mc.multGrid[tv];
-            const Csr& A = cs.accuProl_full[tv];
-            std::vector<int64_t> f2d(g.freeCount.back(), -1);
-            for (int64_t d = 0; d < 3 * g.leveCount.back(); ++d)  // the fine level (not the hanging one)
-                if (g.freeIndex[d] >= 0) f2d[g.freeIndex[d]] = d;
-                else cd.push_back((int32_t)(H.subs[i].dof0 + d));
-            for (int64_t r = 0; r < A.nrow; ++r) {
-                for (int64_t k = A.ptr[r]; k < A.ptr[r + 1]; ++k) {
-                    col.push_back((int32_t)(xoff[i] + A.col[k]));
-                    val.push_back(A.val[k]);
-                }
-                ptr.push_back((int64_t)col.size());
-                tgt.push_back((int32_t)(H.subs[i].dof0 + f2d[r]));
-            }
-        }
-        C.npr = (int64_t)tgt.size();
-        C.ncd = (int64_t)cd.size();
-        // u += accuProl x_c on the free rows (entries, target index, u read + written), the
-        // constrained rows' prescribed values again
-        C.bytes_iter += 12.0 * (double)col.size() + 20.0 * (double)C.npr + 28.0 * (double)C.ncd;
-        C.pptr.upload(ptr);
-        C.pcol.upload(col.empty() ? std::vector<int32_t>{0} : col);
-        C.pval.upload(val.empty() ? std::vector<double>{0.0} : val);
-        C.ptgt.upload(tgt.empty() ? std::vector<int32_t>{0} : tgt);
-        C.cdof.upload(cd.empty() ? std::vector<int32_t>{0} : cd);
+        const CoarseProlongPlan Q = plan_prolong_assembled(mc, T, R.xoff);
+        static_cast<CoarseProlongShape&>(C) = Q;
+        C.bytes_iter += Q.bytes;
+        C.pptr.upload(Q.pptr);
+        C.pcol.upload(Q.pcol);
+        C.pval.upload(Q.pval);
+        C.ptgt.upload(Q.ptgt);
+        C.cdof.upload(Q.cdof);
         return;
     }
-    MgpisDevice& D = *H.mg;
-    const int L = (int)D.lev.size() - 1;
-    // stiffness part: gather level-d device values into the owned coarse rows
-    C.dmin = L;
-    std::map<int, std::pair<std::vector<int32_t>, std::vector<int64_t>>> groups;
-    std::vector<int64_t> xnoff(H.subs.size(), 0);
-    int64_t nxn = 0;
-    for (size_t i = 0; i < H.subs.size(); ++i) {
-        const int64_t tv = H.subs[i].tv;
-        const MULTIGRID& g = mc.multGrid[tv];
-        const int d = (int)mc.doleMcsc[tv];
-        if (g.maxiLeve != L) throw ApiError(DDPCA_EINVAL, "batched subdomains need equal level counts");
-        C.dmin = std::min(C.dmin, d);
-        auto& grp = groups[d];
-        const auto& perm = D.level_perm[d][i];
-        for (int64_t dof = 0; dof < 3 * g.leveCount[d]; ++dof) {
-            const int32_t fi = g.freeIndex[dof];
-            if (fi < 0) continue;
-            grp.first.push_back((int32_t)slot_of(cs.baseReco[tv] + fi, tv));  // the row's own slot
-            grp.second.push_back(3 * (D.lev[d].noff[i] + perm[dof / 3]) + dof % 3);
-        }
-        xnoff[i] = nxn;
-        nxn += 3 * g.leveCount[d];
-    }
-    for (auto& kv : groups) {
+    const CoarseProlongPlan Q = plan_prolong_factored(mc, T, batch_view(H.mg.get()), R.slots, R.xoff);
+    static_cast<CoarseProlongShape&>(C) = Q;
+    for (const KGroupPlan& g : Q.kg) {
         CoarseDev::KGroup G;
-        G.level = kv.first;
-        G.rows.upload(kv.second.first);
-        G.src.upload(kv.second.second);
+        G.level = g.level;
+        G.rows.upload(g.rows);
+        G.src.upload(g.src);
         C.kg.push_back(std::move(G));
     }
-    // xn <- xc, and the accumulated prolongation (fine node -> level-d node) per batch node
-    C.nxn = nxn;
-    std::vector<int32_t> xsrc(std::max<int64_t>(nxn, 1), -1);
-    C.qnn = D.lev.back().nn;
-    std::vector<int32_t> qcol(8 * C.qnn, -1);
-    std::vector<double> qw(8 * C.qnn, 0.0);
-    std::vector<uint8_t> flag(H.NU, 0);
-    std::vector<int64_t> hptr{0};
-    std::vector<int32_t> hcol, htgt;
-    std::vector<double> hval;
-    for (size_t i = 0; i < H.subs.size(); ++i) {
-        const int64_t tv = H.subs[i].tv;
-        const MULTIGRID& g = mc.multGrid[tv];
-        const int d = (int)mc.doleMcsc[tv];
-        for (int64_t dof = 0; dof < 3 * g.leveCount[d]; ++dof) {
-            const int32_t fi = g.freeIndex[dof];
-            xsrc[xnoff[i] + dof] = fi < 0 ? -1 : (int32_t)(xoff[i] + fi);
-        }
-        const Stencil& Q = cs.accuQ[tv];
-        const int64_t b0 = H.subs[i].dof0 / 3;
-        std::vector<int64_t> bo(Q.col.size(), -1);
-        for (size_t q = 0; q < Q.bent.size(); ++q) bo[Q.bent[q]] = (int64_t)q;
-        for (int64_t nd = 0; nd < Q.nf; ++nd) {
-            const int64_t len = Q.ptr[nd + 1] - Q.ptr[nd];
-            bool scalar = len <= 8;
-            for (int64_t k = Q.ptr[nd]; k < Q.ptr[nd + 1] && scalar; ++k) scalar = bo[k] < 0;
-            if (scalar) {
-                for (int64_t k = 0; k < len; ++k) {
-                    qcol[k * C.qnn + b0 + nd] = (int32_t)(xnoff[i] + 3 * Q.col[Q.ptr[nd] + k]);
-                    qw[k * C.qnn + b0 + nd] = Q.w[Q.ptr[nd] + k];
-                }
-                continue;
-            }
-            // a CSR row per free dof over x_c (the scalar kernel adds 0 there and the prescribed
-            // values of the node's constrained dofs)
-            for (int a = 0; a < 3; ++a) {
-                const int64_t dof = 3 * nd + a;
-                if (!g.consFlag[dof]) continue;
-                for (int64_t k = Q.ptr[nd]; k < Q.ptr[nd + 1]; ++k) {
-                    const int64_t c = Q.col[k];
-                    for (int b = 0; b < 3; ++b) {
-                        if (bo[k] < 0 && b != a) continue;
-                        const int32_t f = g.freeIndex[3 * c + b];
-                        const double w = bo[k] < 0 ? Q.w[k] : Q.bval[9 * bo[k] + 3 * a + b];
-                        if (f < 0 || w == 0.0) continue;
-                        hcol.push_back((int32_t)(xoff[i] + f));
-                        hval.push_back(w);
-                    }
-                }
-                hptr.push_back((int64_t)hcol.size());
-                htgt.push_back((int32_t)(H.subs[i].dof0 + dof));
-            }
-        }
-        for (int64_t dof = 0; dof < 3 * g.leveCount.back(); ++dof) flag[H.subs[i].dof0 + dof] = g.consFlag[dof];
+    if (C.npr) {  // the nodes the scalar stencil cannot hold (rotation blocks)
+        C.pptr.upload(Q.pptr);
+        C.pcol.upload(Q.pcol);
+        C.pval.upload(Q.pval);
+        C.ptgt.upload(Q.ptgt);
+        C.bytes_iter += Q.bytes_csr;
     }
-    C.npr = (int64_t)htgt.size();
-    C.ncd = 0;
-    if (C.npr) {
-        C.pptr.upload(hptr);
-        C.pcol.upload(hcol.empty() ? std::vector<int32_t>{0} : hcol);
-        C.pval.upload(hval.empty() ? std::vector<double>{0.0} : hval);
-        C.ptgt.upload(htgt);
-        C.bytes_iter += 12.0 * (double)hcol.size() + 20.0 * (double)C.npr;
-    }
-    C.xsrc.upload(xsrc);
-    C.xn.alloc(std::max<int64_t>(nxn, 1));
-    C.qcol.upload(qcol);
-    C.qw.upload(qw);
-    C.flag.upload(flag);
-    // factored stiffness part and prolongation: K x = b - r (b, r read, the difference written:
-    // 72 B per fine node), the plain restriction chain down to dmin (r_f once, mask + b_c per
-    // coarse node, the lattice's child mask + fine copy or the stencil's index + weight), the
-    // gather of level-d values into g, x_c scattered to nodal xn, and u += (Q (x) I3) xn: Q's
-    // entries, flags, u read + written, xn once
-    double nf = 0.0, qent = 0.0, kp = 0.0;
-    for (size_t i = 0; i < H.subs.size(); ++i) {
-        nf += (double)H.subs[i].nn;
-        qent += (double)cs.accuQ[H.subs[i].tv].col.size();
-        for (int l = L; l > C.dmin; --l) {
-            const LevelDev& F = D.lev[l];
-            kp += 24.0 * (double)F.nloc[i] + (25.0 + (F.lat ? 8.0 : 0.0)) * (double)D.lev[l - 1].nloc[i] +
-                  (F.lat ? 0.0 : 12.0 * (double)F.tent_sub[i]);
-        }
-    }
-    double krows = 0.0;
-    for (auto& kv : groups) krows += (double)kv.second.first.size();
-    C.bytes_iter += 72.0 * nf + kp + 36.0 * krows + 20.0 * (double)nxn + 12.0 * qent + 51.0 * nf + 8.0 * (double)nxn;
+    C.xsrc.upload(Q.xsrc);
+    C.xn.alloc(std::max<int64_t>(C.nxn, 1));
+    C.qcol.upload(Q.qcol);
+    C.qw.upload(Q.qw);
+    C.flag.upload(Q.flag);
+    C.bytes_iter += Q.bytes;
 }
 
 // globCoup_1^-1 rows of the owned subdomains: every rank's rows are summed into a full dense
@@ -1731,23 +941,7 @@ void coarse_invert(ddpca_mcontact& H) {
             H.comm->allreduce_sum(dt.p, (int64_t)trip.size(), H.main);
             DDPCA_HIP(hipStreamSynchronize(H.main));
             trip = dt.download();
-            std::vector<std::vector<std::pair<int32_t, double>>> rows(C.n);
-            for (int64_t q = 0; q < off[H.nranks]; ++q) rows[(int64_t)trip[3 * q]].push_back({(int32_t)trip[3 * q + 1], trip[3 * q + 2]});
-            Csr A;
-            A.nrow = A.ncol = C.n;
-            A.ptr.assign(1, 0);
-            for (auto& row : rows) {
-                std::stable_sort(row.begin(), row.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-                for (size_t k = 0; k < row.size();) {
-                    size_t e = k;
-                    double v = 0.0;
-                    for (; e < row.size() && row[e].first == row[k].first; ++e) v += row[e].second;
-                    A.col.push_back(row[k].first);
-                    A.val.push_back(v);
-                    k = e;
-                }
-                A.ptr.push_back((int64_t)A.col.size());
-            }
+            const Csr A = triplets_to_csr(trip, off[H.nranks], C.n);
             C.gathered_rows = Csr();
             if (!C.plan.nglob.empty()) finish_coarse_mg(H, C, A);
         }
@@ -1761,7 +955,7 @@ void coarse_invert(ddpca_mcontact& H) {
     std::vector<double>().swap(C.dense);
     hipStream_t st = H.main;
     if (H.nranks > 1 && !H.comm) throw ApiError(DDPCA_ESTATE, "the coarse space of a multi-rank run needs mcontact_gpu_comm_init");
-    const bool verbose = std::getenv("DDPCA_VERBOSE") != nullptr;
+    const bool verbose = H.tune.verbose;
     auto checksum = [n](const std::vector<double>& v) {
         double a = 0.0, b = 0.0;
         for (int64_t i = 0; i < n * n; ++i) a += std::abs(v[i]), b += v[i] * (double)(i % 9973);
@@ -2198,8 +1392,9 @@ int mcontact_gpu_create(ddpca_problem_t p, int device, int rank, int nranks, con
         if (opt) H->opt = *opt;
         else mgpis_default_options(&H->opt);
         for (auto& e : H->ev) DDPCA_HIP(hipEventCreate(&e));
-        build(*H, P);
-        build_coarse(*H, P);
+        H->tune = admm_tuning();
+        const AdmmTables T = build(*H, P);
+        build_coarse(*H, P, T);
         if (nranks == 1) coarse_invert(*H);
         prepare_graphs(*H);
         *out = H.release();

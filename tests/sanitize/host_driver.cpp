@@ -1,7 +1,7 @@
 // Sanitizer driver for the host C++ of libddpca_amd (SURVEY §5 "race detection / sanitizers").
 //
 // Built by tests/sanitize/Makefile from the host translation units only (capi_builder, capi_host,
-// capi_multigrid, csearch, errors, lagrange, mass_plan, mcontact, mgpis_plan, multigrid, multiscale, sparse, writers) with
+// capi_multigrid, csearch, errors, lagrange, admm_plan, mass_plan, mcontact, mgpis_plan, multigrid, multiscale, sparse, writers) with
 // -fsanitize=address,undefined; no device objects, no GPU.  It drives the setup code that produces
 // every GPU operand through the C ABI the tests use:
 //   * the problem generators (BEAM single / DD, the two-block contact frictionless and Coulomb,
@@ -20,6 +20,14 @@
 //     plan of a two-member batch with and without coordinates, the value records of every storage
 //     type, lattice and explicit transfers, a nine-parent node, the colour plan, the coarse packing;
 //     on the octree above the block transfer entries and the band of the locally refined fine level;
+//   * the host setup of the ADMM handle (admm_plan.cpp, called directly on the problems cast to
+//     Problem*): the workspace layout and tables, every SELL-64 interface operator, the coupling and
+//     hanging rows against products formed term by term from the Interface's operators (tolerance
+//     (k - 1) eps sum |terms| per row), both branches of the fused decision, the coarse right-hand
+//     side's slots of two-rank layouts against the one-rank plan bit for bit, the
+//     DOUBLE_M_1 and LATIN DOUBLE_M hierarchies, the prolongation tables on the rotated octree, a rank
+//     without subdomains, and the plan's refusals (an entry off the interface graph, baseReco off the
+//     free dofs, a workspace index of 2^31);
 //   * the refused-argument paths (bad indices, reversed pointers) of those entry points.
 // The reference-comparison harnesses (oracle/ref_multigrid, ref_csearch, ref_refine,
 // ref_lagrange_host) are linked to the same sanitized objects by the Makefile's `ref` target.
@@ -29,15 +37,19 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <climits>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <tuple>
 #include <vector>
 
+#include "admm_plan.hpp"
 #include "common.hpp"
 #include "ddpca_amd.h"
 #include "mass_plan.hpp"
 #include "mgpis_plan.hpp"
+#include "problem.hpp"
 #include "subdomain_ops.hpp"
 
 namespace ddpca {
@@ -48,6 +60,7 @@ namespace {
 
 int g_fail = 0;
 void plan_general(const ddpca::MULTIGRID& g);  // the MGPIS plan on run_octree's tree, below
+void admm_plan_octree(ddpca_multigrid_t g);     // the ADMM plan on it as a problem subdomain, below
 
 void ok(int rc, const char* what) {
     if (rc < 0) {
@@ -358,6 +371,7 @@ void run_octree() {
                 (long)nplan, s);
     bool built = false;
     plan_general(*ddpca::multigrid_of(g, &built));
+    admm_plan_octree(g);
     ddpca_multigrid_destroy(g);
 }
 
@@ -1082,6 +1096,668 @@ void run_mgpis_plan() {
     plan_transfers_and_colours();
 }
 
+// ---- the ADMM handle's host setup (admm_plan.cpp), called directly on established problems
+void acheck(bool good, const std::string& what) {
+    if (!good) {
+        std::fprintf(stderr, "FAIL admm_plan: %s\n", what.c_str());
+        ++g_fail;
+    }
+}
+
+// what MgpisDevice would hold of the owned subdomains' batch, from the MGPIS plan alone
+struct HostBatch {
+    std::vector<SubdomainOps> ops;
+    MgpisNumbering num;
+    std::vector<int64_t> noff;  // fine level: first node per member
+    BatchView V;                // (points into num)
+    int64_t fine_dof(int s, int64_t d) const { return 3 * (noff[s] + num.perm.back()[s][d / 3]) + d % 3; }
+};
+std::unique_ptr<HostBatch> host_batch(const MCONTACT& mc, const std::vector<AdmmSub>& subs) {
+    auto B = std::make_unique<HostBatch>();
+    if (subs.empty()) return B;
+    for (const auto& S : subs) B->ops.push_back(subdomain_ops(mc.multGrid[S.tv]));
+    B->num = mgpis_numbering(B->ops, 0);
+    const MgpisTuning tune;
+    const int nlev = (int)B->ops[0].nnodes.size();
+    std::vector<LevelShape> sh;
+    for (int l = 0; l < nlev; ++l) sh.push_back(plan_level(B->ops, B->num, l, true, 0, tune));
+    for (int l = 0; l < nlev; ++l) {
+        BatchLevelView v;
+        v.nn = sh[l].nn;
+        v.noff = sh[l].noff;
+        v.nloc = sh[l].nloc;
+        if (l > 0) {
+            const TransferShape t = plan_transfer(B->ops, B->num, l, sh[l], sh[l - 1], tune);
+            v.tent_sub = t.tent_sub;
+            v.lat = t.lat;
+        }
+        B->V.lev.push_back(v);
+    }
+    B->noff = sh.back().noff;
+    B->V.level_perm = &B->num.perm;
+    for (size_t s = 0; s < subs.size(); ++s)
+        B->V.nfree.push_back((int64_t)free_dof_map(B->ops[s], B->num.perm[nlev - 1][s], B->noff[s]).size());
+    return B;
+}
+
+double wval(int64_t i) { return std::sin(0.37 * (double)i) + 0.1 * std::cos(5.1 * (double)i) + 0.01; }
+
+// a product formed term by term: the sum, the sum of magnitudes and the term count per row
+struct Acc {
+    std::vector<double> y, a;
+    std::vector<int64_t> k;
+    explicit Acc(int64_t n) : y(n, 0.0), a(n, 0.0), k(n, 0) {}
+    void add(int64_t r, double v, double x) {
+        y[r] += v * x;
+        a[r] += std::fabs(v * x);
+        ++k[r];
+    }
+    // |got - y| within (k - 1) eps sum |terms|: both sides sum the same products in another order
+    bool close(int64_t r, double got) const {
+        return std::fabs(got - y[r]) <= (double)std::max<int64_t>(k[r] - 1, 0) * 2.220446049250313e-16 * a[r];
+    }
+};
+
+std::vector<double> sell_apply(const SellPlan& P, const std::vector<double>& W) {
+    std::vector<double> y(P.nrow, 0.0);
+    for (int64_t r = 0; r < P.nrow; ++r)
+        for (int64_t q = P.off[r / 64]; q < P.off[r / 64] + P.slots[r / 64]; ++q) y[r] += P.val[q * 64 + r % 64] * W[P.col[q * 64 + r % 64]];
+    return y;
+}
+
+// the packed operator against the term-by-term product; columns inside W; slots past a row's
+// terms and rows past the product's hold column 0, value 0
+void sell_check(const SellPlan& P, const Acc& ref, const std::vector<double>& W, const std::string& what) {
+    const int64_t nw = (int64_t)W.size(), nr = (int64_t)ref.y.size();
+    bool shape = P.nrow % 64 == 0 && P.nch == P.nrow / 64 && P.nrow >= nr && (int64_t)P.off.size() == P.nch + 1, cols = true, pads = true,
+         prod = true;
+    acheck(shape, what + ": padded rows, chunk count");
+    if (!shape) return;
+    const std::vector<double> y = sell_apply(P, W);
+    for (int64_t r = 0; r < P.nrow; ++r) {
+        const int64_t kr = r < nr ? ref.k[r] : 0;
+        for (int64_t q = P.off[r / 64], j = 0; q < P.off[r / 64 + 1]; ++q, ++j) {
+            const int32_t c = P.col[q * 64 + r % 64];
+            cols = cols && c >= 0 && c < nw;
+            if (j >= kr) pads = pads && c == 0 && P.val[q * 64 + r % 64] == 0.0;
+        }
+        if (r < nr) prod = prod && ref.close(r, y[r]);
+    }
+    acheck(cols, what + ": every column inside W");
+    acheck(pads, what + ": pad slots hold column 0, value 0");
+    acheck(prod, what + ": the packed product equals the term-by-term product within (k - 1) eps sum |terms|");
+}
+
+struct AdmmCase {
+    ddpca_problem_t p = nullptr;
+    Problem* P = nullptr;
+    std::vector<int32_t> owner;
+    int rank = 0;
+    std::unique_ptr<HostBatch> B;
+    AdmmTables T;
+    ~AdmmCase() {
+        if (p) ddpca_problem_destroy(p);
+    }
+};
+
+// tables of (problem, owner, rank) with the layout checks
+void plan_case_tables(AdmmCase& c, const AdmmTuning& tune, const std::string& name) {
+    const MCONTACT& mc = c.P->mc;
+    std::vector<AdmmSub> subs = owned_subdomains(*c.P, c.owner, c.rank);
+    c.B = host_batch(mc, subs);
+    c.T = plan_tables(mc, subs, c.owner, c.rank, c.B->V, tune);
+    const AdmmTables& T = c.T;
+    // regions: 64-aligned, in order, disjoint
+    bool lay = T.oH == T.NU && T.oS == T.oH + T.NH && T.oG == T.oS + 2 * T.R && T.G >= 64;
+    for (int64_t v : {T.NU, T.NH, T.R, T.G, T.oH, T.oS, T.oG}) lay = lay && v % 64 == 0 && v >= 0;
+    std::vector<std::pair<int64_t, int64_t>> useg, hseg, rseg, gseg;
+    for (const auto& S : T.subs) {
+        useg.push_back({S.dof0, S.dof0 + 3 * S.nn});
+        hseg.push_back({S.hoff, S.hoff + S.nh});
+        lay = lay && c.owner[S.tv] == c.rank && S.nn == mc.multGrid[S.tv].leveCount.back();
+    }
+    int64_t nside = 0;
+    for (int64_t ts = 0; ts < T.nint; ++ts)
+        for (int s = 0; s < 2; ++s) nside += c.owner[mc.searCont[ts].body[s]] == c.rank;
+    lay = lay && (int64_t)T.sides.size() == nside && (int64_t)T.itfs.size() == T.nint;
+    for (const auto& sd : T.sides) {
+        rseg.push_back({sd.roff, sd.roff + sd.m});
+        lay = lay && sd.roff % 64 == 0 && sd.tv == mc.searCont[sd.ts].body[sd.s] && c.owner[sd.tv] == c.rank && T.subs[sd.sub].tv == sd.tv;
+    }
+    int64_t last_cross = -1, first_local = INT64_MAX;
+    for (const auto& I : T.itfs) {
+        gseg.push_back({I.goff, I.goff + I.mip});
+        const Interface& itf = mc.searCont[I.ts];
+        const bool cross = c.owner[itf.body[0]] != c.owner[itf.body[1]];
+        lay = lay && I.cross == cross && I.mine == (c.owner[itf.body[0]] == c.rank || c.owner[itf.body[1]] == c.rank) && I.mip == itf.mip();
+        if (cross) last_cross = std::max(last_cross, I.goff);
+        else first_local = std::min(first_local, I.goff);
+    }
+    lay = lay && last_cross < first_local;  // cross-rank interfaces first
+    auto disjoint = [](std::vector<std::pair<int64_t, int64_t>> v, int64_t n) {
+        std::sort(v.begin(), v.end());
+        int64_t end = 0;
+        for (const auto& s : v) {
+            if (s.first < end || s.second > n) return false;
+            end = s.second;
+        }
+        return true;
+    };
+    lay = lay && disjoint(useg, T.NU) && disjoint(hseg, T.NH) && disjoint(rseg, T.R) && disjoint(gseg, T.G);
+    acheck(lay, name + ": W's regions are 64-aligned and disjoint, the tables name the owned sides");
+    std::vector<int32_t> on = T.onode;
+    std::sort(on.begin(), on.end());
+    bool perm = true;
+    for (size_t i = 0; i < on.size(); ++i) perm = perm && on[i] == (int32_t)i;
+    acheck(perm && (int64_t)T.cf.size() == T.NU && (int64_t)T.presc.size() == T.NU, name + ": onode is a permutation");
+    bool mx = T.maxit.size() == T.subs.size();
+    for (size_t i = 0; mx && i < T.subs.size(); ++i) mx = T.maxit[i] == mc.multGrid[T.subs[i].tv].freeCount.back();
+    acheck(mx, name + ": maxit is the free dof count");
+}
+
+// every interface operator of the case, applied to a pseudo-random W
+void plan_case_operators(AdmmCase& c, const std::string& name) {
+    const MCONTACT& mc = c.P->mc;
+    const AdmmTables& T = c.T;
+    const HostBatch& B = *c.B;
+    std::vector<double> W(T.oG + T.G);
+    for (size_t i = 0; i < W.size(); ++i) W[i] = wval((int64_t)i);
+    auto wc = [&](const AdmmSub& S, int64_t col) { return col < 3 * S.nn ? S.dof0 + col : T.oH + S.hoff + (col - 3 * S.nn); };
+    Acc gam(T.G), aux(T.R), lam(T.R), wv(2 * T.R), hang(T.NH), cpl(std::max<int64_t>(T.NU, 1));
+    std::vector<double> gc(T.G, 0.0), ri(std::max<int64_t>(T.R, 1), 0.0);
+    for (const auto& sd : T.sides) {
+        const Interface& itf = mc.searCont[sd.ts];
+        const AdmmItf& I = T.itfs[sd.ts];
+        const AdmmSub& S = T.subs[sd.sub];
+        const int s = (int)sd.s;
+        const int64_t aux0 = T.oS + sd.roff, lam0 = T.oS + T.R + sd.roff, g0 = T.oG + I.goff;
+        const double half = s == 0 ? 0.5 : -0.5;
+        for (int64_t i = 0; i < itf.mip(); ++i) {
+            if (!itf.factored) {
+                for (int64_t k = itf.inpoLagr[s].ptr[i]; k < itf.inpoLagr[s].ptr[i + 1]; ++k)
+                    gam.add(I.goff + i, half * itf.inpoLagr[s].val[k], W[lam0 + itf.inpoLagr[s].col[k]]);
+                for (int64_t k = itf.pemaInpo_r[s].ptr[i]; k < itf.pemaInpo_r[s].ptr[i + 1]; ++k)
+                    gam.add(I.goff + i, half * itf.pemaInpo_r[s].val[k], W[wc(S, itf.pemaInpo_r[s].col[k])]);
+            }
+            if (s == 0) gc[I.goff + i] = -0.5 * (itf.pemaDiag[i] * itf.inpoNgap[i]);
+        }
+        // T^T u without forming the transpose: body dof j, side row c
+        for (int pena = 0; pena < 2; ++pena) {
+            const Csr& A = pena ? itf.systTran_pena[s] : itf.systTran[s];
+            for (int64_t j = 0; j < A.nrow; ++j)
+                for (int64_t k = A.ptr[j]; k < A.ptr[j + 1]; ++k) {
+                    if (pena) {
+                        aux.add(sd.roff + A.col[k], A.val[k], W[wc(S, j)]);
+                        lam.add(sd.roff + A.col[k], A.val[k], W[wc(S, j)]);
+                    } else {
+                        wv.add(sd.roff + A.col[k], A.val[k], W[wc(S, j)]);
+                    }
+                }
+        }
+        for (int64_t r = 0; r < itf.mside(s); ++r) {
+            for (int64_t k = itf.inteMass[s].ptr[r]; k < itf.inteMass[s].ptr[r + 1]; ++k)
+                aux.add(sd.roff + r, itf.inteMass[s].val[k], W[lam0 + itf.inteMass[s].col[k]]);
+            for (int64_t k = itf.inteInpo[s].ptr[r]; k < itf.inteInpo[s].ptr[r + 1]; ++k) {
+                aux.add(sd.roff + r, itf.inteInpo[s].val[k], W[g0 + itf.inteInpo[s].col[k]]);
+                if (!itf.factored) wv.add(T.R + sd.roff + r, itf.inteInpo[s].val[k], W[g0 + itf.inteInpo[s].col[k]]);
+            }
+            for (int64_t k = itf.inteMass_pena[s].ptr[r]; k < itf.inteMass_pena[s].ptr[r + 1]; ++k)
+                lam.add(sd.roff + r, -itf.inteMass_pena[s].val[k], W[aux0 + itf.inteMass_pena[s].col[k]]);
+            ri[sd.roff + r] = 1.0 / itf.penN;
+        }
+        // coupling rows: [systTran_pena | -systTran] on the free dofs, hanging rows through hangProl
+        const MULTIGRID& g = mc.multGrid[sd.tv];
+        const Csr& Tp = itf.systTran_pena[s];
+        const Csr& Tr = itf.systTran[s];
+        for (int64_t r = 0; r < Tp.nrow; ++r) {
+            std::vector<std::pair<int64_t, double>> tgt;
+            if (r < 3 * S.nn) tgt.push_back({r, 1.0});
+            else
+                for (int64_t k = g.hangProl.ptr[r - 3 * S.nn]; k < g.hangProl.ptr[r - 3 * S.nn + 1]; ++k)
+                    tgt.push_back({g.hangProl.col[k], g.hangProl.val[k]});
+            for (const auto& t : tgt) {
+                if (!g.consFlag[t.first] || t.second == 0.0) continue;
+                const int64_t row = B.fine_dof(sd.sub, t.first);
+                for (int64_t k = Tp.ptr[r]; k < Tp.ptr[r + 1]; ++k) cpl.add(row, t.second * Tp.val[k], W[aux0 + Tp.col[k]]);
+                for (int64_t k = Tr.ptr[r]; k < Tr.ptr[r + 1]; ++k) cpl.add(row, -t.second * Tr.val[k], W[lam0 + Tr.col[k]]);
+            }
+        }
+    }
+    int64_t nhang = 0;
+    for (const auto& S : T.subs) {
+        const Csr& Hp = mc.multGrid[S.tv].hangProl;
+        nhang += S.nh;
+        for (int64_t r = 0; r < S.nh; ++r)
+            for (int64_t k = Hp.ptr[r]; k < Hp.ptr[r + 1]; ++k) hang.add(S.hoff + r, Hp.val[k], W[wc(S, Hp.col[k])]);
+    }
+    // ---- the planned operators
+    const AdmmOperators O = plan_operators(mc, T, false);
+    {
+        // gamma = the side-0 rows plus the rank-local side-1 halves scattered onto them
+        std::vector<double> y = sell_apply(O.gamma, W);
+        bool dst = true;
+        if (O.has_gamma1) {
+            const std::vector<double> y1 = sell_apply(O.gamma1, W);
+            for (size_t j = 0; j < O.gam1_dst.size(); ++j) {
+                dst = dst && O.gam1_dst[j] >= 0 && O.gam1_dst[j] < T.G;
+                if (dst) y[O.gam1_dst[j]] += y1[j];
+            }
+            for (int32_t cc : O.gamma1.col) dst = dst && cc >= 0 && cc < (int32_t)W.size();
+        }
+        bool prod = (int64_t)y.size() == T.G;
+        for (int64_t r = 0; prod && r < T.G; ++r) prod = gam.close(r, y[r]);
+        for (int32_t cc : O.gamma.col) dst = dst && cc >= 0 && cc < (int32_t)W.size();
+        acheck(dst && prod, name + ": gamma halves equal +-1/2 (inpoLagr lambda + pemaInpo_r u)");
+        acheck(O.gcst == gc, name + ": gamma's constant part");
+    }
+    sell_check(O.aux, aux, W, name + " op_aux");
+    sell_check(O.lam, lam, W, name + " op_lam");
+    const AdmmOperators Of = plan_operators(mc, T, true);
+    acheck(Of.aux.nch == 0 && Of.lam.nch == 0 && Of.gamma.col == O.gamma.col && Of.gamma.val == O.gamma.val,
+           name + ": the fused update plans no aux / lambda rows, the same gamma");
+    if (!T.sides.empty()) {
+        const AdmmFused F = plan_fused(mc, T);
+        sell_check(F.wv, wv, W, name + " op_wv");
+        acheck(F.rinv == ri, name + ": rinv = 1 / penN on the sides' rows");
+    }
+    for (int which = 0; which < 3; ++which) {
+        const MassList L = mass_list(mc, T, which);
+        bool good = L.A.size() == (which == 2 ? 2 : 1) * T.sides.size() && L.roff.size() == L.A.size() && L.nrow == (which == 2 ? 2 : 1) * T.R;
+        for (size_t i = 0; good && i < L.A.size(); ++i) {
+            const AdmmSide& sd = T.sides[i % T.sides.size()];
+            const Interface& itf = mc.searCont[sd.ts];
+            good = L.A[i] == (which == 0 ? &itf.inteMass_pena[sd.s] : &itf.inteMass[sd.s]) &&
+                   L.roff[i] == sd.roff + (int64_t)(i / T.sides.size()) * T.R;
+        }
+        acheck(good, name + ": the mass batches' systems and row offsets");
+    }
+    {
+        const CouplingPlan K = plan_coupling(mc, T, B.V);
+        bool good = K.cptr.size() == K.crow.size() + 1 && K.ccol.size() == K.cval.size(), rows = true;
+        std::vector<char> seen(cpl.y.size(), 0);
+        for (size_t i = 0; good && i < K.crow.size(); ++i) {
+            double y = 0.0;
+            for (int64_t k = K.cptr[i]; k < K.cptr[i + 1]; ++k) {
+                good = good && K.ccol[k] >= T.oS && K.ccol[k] < T.oG && (k == K.cptr[i] || K.ccol[k] > K.ccol[k - 1]);
+                if (good) y += K.cval[k] * W[K.ccol[k]];
+            }
+            good = good && K.crow[i] >= 0 && K.crow[i] < T.NU && !seen[K.crow[i]] && cpl.close(K.crow[i], y);
+            if (good) seen[K.crow[i]] = 1;
+        }
+        for (size_t r = 0; r < cpl.y.size(); ++r) rows = rows && (seen[r] != 0) == (cpl.k[r] > 0);
+        acheck(good, name + ": coupling rows equal [systTran_pena | -systTran] folded through hangProl, columns merged");
+        acheck(rows, name + ": a coupling row for every coupled free dof and no other");
+    }
+    if (T.NH) sell_check(plan_hanging(mc, T), hang, W, name + " op_hang");
+    // factored per-ip operands: indices inside W's lambda / u regions, shape values as the ips'
+    int64_t nfact = 0;
+    for (const AdmmItf& I : T.itfs) {
+        const Interface& itf = mc.searCont[I.ts];
+        if (!I.mine || !itf.factored) continue;
+        ++nfact;
+        const FactItfPlan F = plan_factored(mc, T, I);
+        bool good = F.nip == (int64_t)itf.ip.size() && F.C == itf.comp() && F.goff == I.goff;
+        for (int s = 0; s < 2 && good; ++s) {
+            good = (F.own[s] != 0) == (c.owner[itf.body[s]] == c.rank);
+            if (!F.own[s]) continue;
+            const AdmmSide& sd = T.sides[T.side_of.at({I.ts, s})];
+            const AdmmSub& S = T.subs[sd.sub];
+            for (int64_t q = 0; q < F.nip && good; ++q)
+                for (int a = 0; a < 4 && good; ++a) {
+                    const int64_t node = itf.ip[q].node[s][a];
+                    const auto at = std::find(itf.nodeCont[s].begin(), itf.nodeCont[s].end(), node) - itf.nodeCont[s].begin();
+                    good = F.M[s][a * F.nip + q] == itf.ip[q].shap[s][a] && F.lam[s][a * F.nip + q] == T.oS + T.R + sd.roff + F.C * at &&
+                           F.u[s][a * F.nip + q] == wc(S, 3 * node);
+                }
+            good = good && F.nnc[s] == (int64_t)itf.nodeCont[s].size() && F.nptr[s].size() == (size_t)F.nnc[s] + 1 &&
+                   F.nptr[s].back() == 4 * F.nip && F.roff[s] == sd.roff;
+        }
+        acheck(good, name + ": factored per-ip operands index the side's lambda and the body's u");
+    }
+    std::printf("{\"case\": \"admm_plan\", \"problem\": \"%s\", \"rank\": %d, \"W\": %lld, \"sides\": %zu, \"factored\": %lld, \"hanging_dofs\": %lld}\n",
+                name.c_str(), c.rank, (long long)W.size(), T.sides.size(), (long long)nfact, (long long)nhang);
+}
+
+std::unique_ptr<AdmmCase> admm_case(const char* kind, const std::vector<double>& params, int64_t musc, int ranks, int rank,
+                                    const std::vector<int32_t>* owner_in = nullptr) {
+    auto c = std::make_unique<AdmmCase>();
+    ok(ddpca_problem_create(kind, params.data(), (int)params.size(), &c->p), kind);
+    if (!c->p) return nullptr;
+    c->P = reinterpret_cast<Problem*>(c->p);
+    const int64_t nsub = (int64_t)c->P->mc.multGrid.size();
+    std::vector<int64_t> dole(nsub, 1);
+    if (musc) ok(ddpca_problem_set_coarse(c->p, musc, dole.data()), "set_coarse");
+    c->owner.assign(nsub, 0);
+    for (int64_t tv = 0; tv < nsub; ++tv) c->owner[tv] = owner_in ? (*owner_in)[tv] : (int32_t)(tv * ranks / nsub);
+    c->rank = rank;
+    if (ranks == 1) ok(ddpca_problem_establish(c->p), "establish");
+    else ok(ddpca_problem_establish_owned(c->p, c->owner.data(), rank), "establish_owned");
+    return c;
+}
+
+// which (region, subdomain or side, local index) a workspace column is
+std::array<int64_t, 3> locate(const AdmmTables& T, int64_t w) {
+    if (w < T.oH) {
+        for (const auto& S : T.subs)
+            if (w >= S.dof0 && w < S.dof0 + 3 * S.nn) return {0, S.tv, w - S.dof0};
+    } else if (w < T.oS) {
+        for (const auto& S : T.subs)
+            if (w >= T.oH + S.hoff && w < T.oH + S.hoff + S.nh) return {0, S.tv, 3 * S.nn + (w - T.oH - S.hoff)};
+    } else if (w < T.oG) {
+        const int64_t half = w < T.oS + T.R ? 0 : 1, r = w - T.oS - half * T.R;
+        for (const auto& sd : T.sides)
+            if (r >= sd.roff && r < sd.roff + sd.m) return {1 + half, 2 * sd.ts + sd.s, r - sd.roff};
+    }
+    return {-1, -1, -1};
+}
+
+// the coarse right-hand side's slots of an R-rank layout against the one-rank plan
+void coarse_rank_invariance(const char* kind, const std::vector<double>& params, int64_t musc, const std::vector<int32_t>& owner,
+                            int ranks, const std::string& name) {
+    const AdmmTuning tune;
+    auto one = admm_case(kind, params, musc, 1, 0);
+    if (!one) return;
+    plan_case_tables(*one, tune, name + " r1");
+    const CoarseRhsPlan R1 = plan_coarse_rhs(one->P->mc, one->T);
+    const CoarseSpace& cs1 = one->P->mc.coarse;
+    const int64_t n = cs1.n;
+    // the row's own subdomain (none for LATIN's contact rows)
+    std::vector<int64_t> row_tv(n, -1);
+    for (int64_t tv = 0; tv + 1 < (int64_t)cs1.baseReco.size(); ++tv)
+        for (int64_t r = cs1.baseReco[tv]; r < cs1.baseReco[tv + 1]; ++r) row_tv[r] = tv;
+    bool sp = true, vals = true, cols = true, empty = true, f0 = true, srcs = true;
+    int64_t nonempty = 0;
+    for (int rank = 0; rank < ranks; ++rank) {
+        auto c = admm_case(kind, params, musc, ranks, rank, &owner);
+        if (!c) return;
+        plan_case_tables(*c, tune, name + " rank " + std::to_string(rank));
+        const CoarseRhsPlan R = plan_coarse_rhs(c->P->mc, c->T);
+        sp = sp && R.slots.sptr == R1.slots.sptr && R.nslot == R1.nslot;
+        srcs = srcs && R.slots.srcs == R1.slots.srcs;
+        if (!sp || !srcs) break;
+        for (int64_t r = 0; r < n; ++r)
+            for (int64_t j = 0; j < (int64_t)R.slots.srcs[r].size(); ++j) {
+                const int64_t q = R.slots.sptr[r] + j, tv = R.slots.srcs[r][j];
+                const int64_t b = R.rptr[q], e = R.rptr[q + 1], b1 = R1.rptr[q], e1 = R1.rptr[q + 1];
+                if (owner[tv] != rank) {
+                    empty = empty && b == e && R.f0[q] == 0.0;
+                    continue;
+                }
+                vals = vals && e - b == e1 - b1;
+                for (int64_t k = 0; vals && k < e - b; ++k) {
+                    vals = std::memcmp(&R.rval[b + k], &R1.rval[b1 + k], sizeof(double)) == 0;
+                    const auto at = locate(c->T, R.rcol[b + k]);
+                    cols = cols && at[0] >= 0 && at == locate(one->T, R1.rcol[b1 + k]);
+                }
+                nonempty += e > b;
+                // globForc_1 in the row's own slot on its owner, zero in every other slot
+                f0 = f0 && (tv == row_tv[r] ? std::memcmp(&R.f0[q], &R1.f0[q], sizeof(double)) == 0 && R1.f0[q] == cs1.globForc_1[r]
+                                            : R.f0[q] == 0.0 && R1.f0[q] == 0.0);
+            }
+    }
+    acheck(sp && srcs, name + ": sptr and the slots' sources are the same on every rank");
+    acheck(vals && nonempty > 0, name + ": the owner's value sequence of every slot equals the one-rank plan's bitwise");
+    acheck(cols, name + ": every column maps back to the same (subdomain or side, local column)");
+    acheck(empty, name + ": a non-owner's slot is empty");
+    acheck(f0, name + ": f0 is non-zero only in the row's own slot on its owner");
+    std::printf("{\"case\": \"admm_plan_rank_invariance\", \"problem\": \"%s\", \"ranks\": %d, \"rows\": %lld, \"slots\": %lld, \"filled\": %lld}\n",
+                name.c_str(), ranks, (long long)n, (long long)R1.nslot, (long long)nonempty);
+}
+
+// DOUBLE_M(_1): forced by the row threshold; the hierarchy's numbering restated level by level
+void coarse_mg_case(const char* kind, const std::vector<double>& params, int64_t musc, const std::string& name) {
+    auto c = admm_case(kind, params, musc, 1, 0);
+    if (!c) return;
+    MCONTACT& mc = c->P->mc;
+    const CoarseSpace& cs = mc.coarse;
+    AdmmTuning tune;
+    acheck(!coarse_solve_choice(cs, cs.n, 1, tune).mg, name + ": the dense solve by default");
+    tune.coarse_mg_min = 1;
+    const CoarseSolveChoice ch = coarse_solve_choice(cs, cs.n, 1, tune);
+    acheck(ch.mg && !ch.mg_gather && ch.dense_bytes == 8.0 * (double)cs.n * (double)cs.n, name + ": a row threshold of 1 takes the multigrid solve");
+    const MgPlan PL = plan_coarse_mg(mc, cs.n);
+    const int64_t Lc = (int64_t)PL.nglob.size() - 1, nsub = (int64_t)mc.multGrid.size();
+    bool mono = Lc == *std::max_element(mc.doleMcsc.begin(), mc.doleMcsc.end()) && PL.latin == cs.latin, ident = (int64_t)PL.S.size() == Lc;
+    for (int64_t l = 1; l <= Lc; ++l) mono = mono && PL.nglob[l] >= PL.nglob[l - 1];
+    for (int64_t l = 1; ident && l <= Lc; ++l) {
+        const Stencil& S = PL.S[l - 1];
+        ident = S.nf == PL.nglob[l] && S.nc == PL.nglob[l - 1] && (int64_t)S.ptr.size() == S.nf + 1;
+        for (int64_t i = 0; ident && i < PL.nglob[l - 1]; ++i) ident = S.ptr[i + 1] - S.ptr[i] == 1 && S.col[S.ptr[i]] == i && S.w[S.ptr[i]] == 1.0;
+        for (int32_t cc : S.col) ident = ident && cc >= 0 && cc < S.nc;
+    }
+    acheck(mono, name + ": nglob is non-decreasing");
+    acheck(ident, name + ": the rows of a level's carried nodes are identity rows");
+    std::vector<int32_t> f = PL.fdg;
+    std::sort(f.begin(), f.end());
+    bool inj = (int64_t)f.size() == cs.n && std::adjacent_find(f.begin(), f.end()) == f.end();
+    for (int32_t d : PL.fdg) inj = inj && d >= 0 && d < 3 * PL.nglob[Lc] && PL.flev[Lc][d] == 1;
+    acheck(inj, name + ": fdg is injective and lands on dofs flagged free at Lc");
+    // level l = level l - 1's nodes, then every subdomain's new nodes in order (then LATIN's new
+    // contact nodes): a subdomain node's flags are its consFlag
+    bool pre = (int64_t)PL.flev.size() == Lc + 1;
+    std::vector<std::vector<int64_t>> gid(nsub);
+    for (int64_t l = 0; pre && l <= Lc; ++l) {
+        int64_t cnt = l ? PL.nglob[l - 1] : 0;
+        for (int64_t tv = 0; tv < nsub; ++tv) {
+            const int64_t lv = std::max<int64_t>(0, mc.doleMcsc[tv] - (Lc - l));
+            while ((int64_t)gid[tv].size() < mc.multGrid[tv].leveCount[lv]) gid[tv].push_back(cnt++);
+            for (size_t j = 0; pre && j < gid[tv].size(); ++j)
+                for (int a = 0; a < 3; ++a) pre = gid[tv][j] < PL.nglob[l] && PL.flev[l][3 * gid[tv][j] + a] == mc.multGrid[tv].consFlag[3 * j + a];
+        }
+        pre = pre && cnt <= PL.nglob[l] && (cs.latin || cnt == PL.nglob[l]) && (int64_t)PL.flev[l].size() == 3 * PL.nglob[l];
+    }
+    acheck(pre, name + ": flev[l] on a subdomain's nodes is its consFlag prefix");
+    // refused: baseReco not matching the free dofs
+    mc.coarse.baseReco[1] += 1;
+    bool thrown = false;
+    try {
+        plan_coarse_mg(mc, cs.n);
+    } catch (const ApiError& e) {
+        thrown = e.code == DDPCA_EINVAL;
+    }
+    mc.coarse.baseReco[1] -= 1;
+    acheck(thrown, name + ": baseReco not matching the free dofs is refused");
+    std::printf("{\"case\": \"admm_plan_coarse_mg\", \"problem\": \"%s\", \"levels\": %lld, \"nodes\": %lld, \"rows\": %lld}\n", name.c_str(),
+                (long long)(Lc + 1), (long long)PL.nglob[Lc], (long long)cs.n);
+}
+
+// the coarse tables of one case: assembled / factored prolongation inside their ranges
+void plan_case_coarse(AdmmCase& c, const std::string& name, bool want_csr_rows) {
+    const MCONTACT& mc = c.P->mc;
+    const CoarseSpace& cs = mc.coarse;
+    const AdmmTables& T = c.T;
+    const CoarseRhsPlan R = plan_coarse_rhs(mc, T);
+    bool rhs = (int64_t)R.rptr.size() == R.nslot + 1 && (int64_t)R.slots.sptr.size() == cs.n + 1 && (int64_t)R.f0.size() == std::max<int64_t>(R.nslot, 1);
+    for (int64_t k = 0; rhs && k < R.rptr.back(); ++k) rhs = R.rcol[k] >= 0 && R.rcol[k] < T.oG;
+    acheck(rhs, name + ": the coarse right-hand side's columns lie in u, aux and lambda");
+    const int64_t nown = (int64_t)R.own_rows.size();
+    const std::vector<double> dense = coarse_dense_rows(cs, R.own_rows, c.rank);
+    bool dn = (int64_t)dense.size() == cs.n * cs.n;
+    for (int64_t r : R.own_rows)
+        for (int64_t k = cs.globCoup_1.ptr[r]; dn && k < cs.globCoup_1.ptr[r + 1]; ++k) dn = dense[r * cs.n + cs.globCoup_1.col[k]] == cs.globCoup_1.val[k];
+    acheck(dn, name + ": the dense rows hold globCoup_1's owned rows");
+    if (T.subs.empty() || cs.latin) return;
+    const CoarseProlongPlan Q = cs.assembled ? plan_prolong_assembled(mc, T, R.xoff) : plan_prolong_factored(mc, T, c.B->V, R.slots, R.xoff);
+    bool pr = (int64_t)Q.pptr.size() == Q.npr + 1 || (Q.npr == 0 && Q.pptr.size() == 1);
+    for (int64_t r = 0; pr && r < Q.npr; ++r) {
+        pr = Q.ptgt[r] >= 0 && Q.ptgt[r] < T.NU;
+        for (int64_t k = Q.pptr[r]; pr && k < Q.pptr[r + 1]; ++k) pr = Q.pcol[k] >= 0 && Q.pcol[k] < nown;
+    }
+    if (!cs.assembled) {
+        pr = pr && (int64_t)Q.qcol.size() == 8 * Q.qnn && (int64_t)Q.xsrc.size() == std::max<int64_t>(Q.nxn, 1) && (int64_t)Q.flag.size() == T.NU;
+        for (int32_t q : Q.qcol) pr = pr && q >= -1 && q + 2 < Q.nxn;
+        for (int32_t x : Q.xsrc) pr = pr && x >= -1 && x < nown;
+        int64_t krows = 0;
+        for (const auto& g : Q.kg) {
+            pr = pr && g.rows.size() == g.src.size() && g.level >= Q.dmin && g.level < (int)c.B->V.lev.size();
+            for (size_t i = 0; pr && i < g.rows.size(); ++i) pr = g.rows[i] >= 0 && g.rows[i] < R.nslot && g.src[i] >= 0 && g.src[i] < 3 * c.B->V.lev[g.level].nn;
+            krows += (int64_t)g.rows.size();
+        }
+        pr = pr && krows == nown;  // every owned coarse row takes its stiffness part once
+    }
+    acheck(pr, name + ": the prolongation tables and gather groups stay inside xc, xn, u and the slots");
+    if (want_csr_rows) acheck(Q.npr > 0, name + ": a rotated node takes the CSR branch of the factored prolongation");
+    std::printf("{\"case\": \"admm_plan_coarse\", \"problem\": \"%s\", \"rank\": %d, \"own_rows\": %lld, \"csr_rows\": %lld, \"groups\": %zu}\n",
+                name.c_str(), c.rank, (long long)nown, (long long)Q.npr, Q.kg.size());
+}
+
+void run_admm_plan() {
+    AdmmTuning tune;
+    // the two-block contact, frictionless and Coulomb, muscSett 0 / 1 (LATIN) / 2; each once as built
+    // (factored per-ip operators) and once with the operators taken as a caller's (SELL gamma rows)
+    for (double fric : {0.0, 0.3})
+        for (int64_t musc : {0, 1, 2})
+            for (int as_callers = 0; as_callers < 2; ++as_callers) {
+                auto c = admm_case("twoblock", {fric, 2}, musc, 1, 0);
+                if (!c) continue;
+                if (as_callers)
+                    for (auto& itf : c->P->mc.searCont) itf.factored = false;
+                const std::string name = std::string("twoblock comp ") + (fric == 0.0 ? "1" : "3") + " musc " + std::to_string(musc) +
+                                         (as_callers ? " (caller's operators)" : "");
+                plan_case_tables(*c, tune, name);
+                plan_case_operators(*c, name);
+                if (musc) plan_case_coarse(*c, name, false);
+                if (!as_callers) {
+                    // both branches of the fused decision
+                    AdmmTuning off;
+                    off.mass_fused = false;
+                    const bool fu = fused_update(c->P->mc, c->T, tune);
+                    acheck(fu && !fused_update(c->P->mc, c->T, off), name + ": fused by default (proportional penalty operators), sequential with the flag off");
+                    Interface& itf = c->P->mc.searCont[0];
+                    const double keep = itf.inteMass_pena[0].val[0];
+                    itf.inteMass_pena[0].val[0] *= 1.0 + 1e-9;
+                    acheck(!fused_update(c->P->mc, c->T, tune), name + ": a penalty mass entry off the multiple ends the fused update");
+                    itf.inteMass_pena[0].val[0] = keep;
+                }
+            }
+    // the synthetic chain at its smallest: one rank, and two ranks with a cross-rank and a rank-local
+    // interface on each (owner [0, 0, 1, 1]: the contacts rank-local, the glued links across)
+    const std::vector<double> chain = {2, 2, 2, 1, 2, 0.3};
+    for (int64_t musc : {2, 1}) {
+        const std::vector<int32_t> owner = {0, 0, 1, 1};
+        for (int ranks : {1, 2})
+            for (int rank = 0; rank < ranks; ++rank)
+                for (int as_callers = 0; as_callers < 2; ++as_callers) {
+                    auto c = admm_case("dehw", chain, musc, ranks, rank, ranks == 2 ? &owner : nullptr);
+                    if (!c) continue;
+                    if (as_callers)
+                        for (auto& itf : c->P->mc.searCont) itf.factored = false;
+                    const std::string name = "chain musc " + std::to_string(musc) + " ranks " + std::to_string(ranks) + (as_callers ? " (caller's operators)" : "");
+                    plan_case_tables(*c, tune, name);
+                    plan_case_operators(*c, name);
+                    if (!as_callers) plan_case_coarse(*c, name, false);
+                }
+        coarse_rank_invariance("dehw", chain, musc, owner, 2, "chain musc " + std::to_string(musc));
+        coarse_mg_case("dehw", chain, musc, std::string("chain ") + (musc == 2 ? "DOUBLE_M_1" : "LATIN DOUBLE_M"));
+    }
+    coarse_rank_invariance("dehw", chain, 2, {0, 1, 0, 1}, 2, "chain musc 2, contacts across the ranks");
+    // the chain's general mesh (contact band refined once more: a hanging level; rotated support nodes)
+    {
+        auto c = admm_case("dehw", {2, 2, 2, 1, 2, 0.3, 0, 0, 1, 1}, 2, 1, 0);
+        if (c) {
+            plan_case_tables(*c, tune, "general chain");
+            int64_t nh = 0;
+            for (const auto& S : c->T.subs) nh += S.nh;
+            acheck(nh > 0 && c->T.NH >= nh, "general chain: a hanging level");
+            plan_case_operators(*c, "general chain");
+            for (auto& itf : c->P->mc.searCont) itf.factored = false;
+            plan_case_operators(*c, "general chain (caller's operators)");
+            plan_case_coarse(*c, "general chain", false);
+        }
+    }
+    // a rank that owns nothing: the empty view, NU = 64, empty tables
+    {
+        const std::vector<int32_t> owner = {1, 1, 1, 1};
+        auto c = admm_case("dehw", chain, 2, 2, 0, &owner);
+        if (c) {
+            plan_case_tables(*c, tune, "rank without subdomains");
+            acheck(c->B->V.empty() && c->T.NU == 64 && c->T.NH == 0 && c->T.R == 0 && c->T.subs.empty() && c->T.sides.empty(),
+                   "rank without subdomains: NU = 64, empty tables");
+            plan_case_operators(*c, "rank without subdomains");
+            const CoarseRhsPlan R = plan_coarse_rhs(c->P->mc, c->T);
+            acheck(R.own_rows.empty() && R.rptr.back() == 0, "rank without subdomains: empty coarse slots");
+        }
+    }
+    // refusals
+    {
+        auto c = admm_case("dehw", chain, 2, 1, 0);
+        if (c) {
+            plan_case_tables(*c, tune, "refusals");
+            CoarseSpace& cs = c->P->mc.coarse;
+            // subdomains 0 and 3 share no interface: an entry of subdomain 0 in a row of subdomain 3
+            bool graph = true;
+            for (const auto& itf : c->P->mc.searCont) graph = graph && !((itf.body[0] == 0 && itf.body[1] == 3) || (itf.body[0] == 3 && itf.body[1] == 0));
+            acheck(graph, "refusals: subdomains 0 and 3 are no interface mates");
+            Csr& A = cs.globTran_S[0];
+            const Csr keep = A;
+            const int64_t r = cs.baseReco[3];
+            A.col.insert(A.col.begin() + A.ptr[r + 1], 0);
+            A.val.insert(A.val.begin() + A.ptr[r + 1], 1.0);
+            for (int64_t i = r + 1; i <= A.nrow; ++i) ++A.ptr[i];
+            bool thrown = false;
+            try {
+                plan_coarse_rhs(c->P->mc, c->T);
+            } catch (const ApiError& e) {
+                thrown = e.code == DDPCA_EINVAL;
+            }
+            A = keep;
+            acheck(thrown, "refusals: an entry of a subdomain that is not on the row's interface graph");
+        }
+        bool thrown = false, fits = w32(INT32_MAX) == INT32_MAX && w32(0) == 0;
+        try {
+            w32((int64_t)1 << 31);
+        } catch (const ApiError& e) {
+            thrown = e.code == DDPCA_EINVAL;
+        }
+        acheck(thrown && fits, "refusals: a W index of 2^31 does not narrow to int32");
+        Rows rows(1);
+        rows[0].push_back({(int64_t)1 << 31, 1.0});
+        thrown = false;
+        try {
+            sell_pack(rows);
+        } catch (const ApiError& e) {
+            thrown = e.code == DDPCA_EINVAL;
+        }
+        acheck(thrown, "refusals: sell_pack refuses a column of 2^31");
+        std::vector<std::pair<int32_t, double>> row = {{5, 1.0}, {2, 0.5}, {5, 2.0}, {2, 0.25}, {7, -1.0}};
+        sum_duplicates(row);
+        acheck(row == std::vector<std::pair<int32_t, double>>({{2, 0.75}, {5, 3.0}, {7, -1.0}}), "sum_duplicates sorts by column and sums in input order");
+        const Csr M = triplets_to_csr({1, 0, 2.0, 0, 1, 1.0, 1, 0, 3.0}, 3, 2);
+        acheck(M.ptr == std::vector<int64_t>({0, 1, 2}) && M.col == std::vector<int32_t>({1, 0}) && M.val == std::vector<double>({1.0, 5.0}),
+               "triplets_to_csr sums duplicate entries");
+        acheck(count_distinct(std::vector<int32_t>{3, 1, 3, 2, 1}) == 3, "count_distinct");
+        std::printf("{\"case\": \"admm_plan_refusals\"}\n");
+    }
+}
+
+// the refined octree as the one subdomain of a problem with an interface-eliminated coarse space on
+// level 1: a hanging level (nh > 0) and rotated nodes (the CSR rows of the factored prolongation)
+void admm_plan_octree(ddpca_multigrid_t g) {
+    AdmmCase c;
+    ok(ddpca_problem_empty(1, 0, &c.p), "problem_empty");
+    if (!c.p) return;
+    // the tree-built grid itself (as ESTABLISH leaves a generator's: MULTISCALE_1 composes its stencils)
+    c.P = reinterpret_cast<Problem*>(c.p);
+    c.owner = {0};
+    MCONTACT& mc = c.P->mc;
+    bool built = false;
+    mc.multGrid[0] = *multigrid_of(g, &built);
+    if (mc.multGrid[0].nodeAll) mc.multGrid[0].hangProl = mc.multGrid[0].hangRows();
+    c.P->owned = {1};
+    c.P->established = true;
+    mc.muscSett = 2;
+    mc.doleMcsc = {1};
+    try {
+        mc.MULTISCALE_1(nullptr);
+        plan_case_tables(c, AdmmTuning(), "octree");
+        acheck(c.T.subs.size() == 1 && c.T.subs[0].nh > 0 && c.T.NH >= c.T.subs[0].nh, "octree: a hanging level");
+        plan_case_operators(c, "octree");
+        plan_case_coarse(c, "octree", true);
+    } catch (const std::exception& e) {
+        acheck(false, std::string("octree: ") + e.what());
+    }
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -1118,6 +1794,7 @@ int main(int argc, char** argv) {
     run_writers();
     run_mass_plan();
     run_mgpis_plan();
+    run_admm_plan();
     std::printf("{\"ok\": %s, \"failures\": %d}\n", g_fail ? "false" : "true", g_fail);
     return g_fail ? 1 : 0;
 }
