@@ -181,6 +181,7 @@ struct MirrorBuf {
     ~MirrorBuf();
 };
 
+// (select_device, MirrorBuf and the pacing below: device_common.hip)
 // Replay `graph` (k iterations each) on `stream` until every mirror reports done, keeping
 // about one replay queued ahead of the slowest unfinished solve.  `launched` = iterations
 // already enqueued (eager + pre-enqueued replays).  Returns the number of replays launched.

@@ -24,8 +24,6 @@
 // (device_mass.hpp); the ranks' exchanges go through a Transport (device_transport.hpp).
 // Everything runs on the batch's single stream.
 #include <hip/hip_runtime.h>
-#include <rocblas/rocblas.h>
-#include <rocsolver/rocsolver.h>
 
 #include <algorithm>
 #include <chrono>
@@ -37,6 +35,7 @@
 
 #include "../../include/ddpca_amd.h"
 #include "admm_plan.hpp"
+#include "device_dense.hpp"
 #include "device_eigs.hpp"
 #include "device_mass.hpp"
 #include "device_mgpis.hpp"
@@ -439,15 +438,6 @@ __global__ void k_perm_scatter(const int32_t* perm, const double* g, double* b, 
 __global__ void k_perm_gather(const int32_t* perm, const int32_t* rows, const double* x, double* xc, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) xc[i] = x[perm[rows[i]]];
-}
-
-// potri(lower) on the column-major view leaves the inverse in the row-major upper triangle;
-// mirror it into the lower one
-__global__ void k_fill_lower(double* A, int64_t n) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * n) return;
-    const int64_t i = idx / n, j = idx % n;
-    if (j < i) A[i * n + j] = A[j * n + i];
 }
 
 // Fused interface update (penalty mass operators proportional to the plain ones, rho = penN =
@@ -973,23 +963,18 @@ void coarse_invert(ddpca_mcontact& H) {
         std::fprintf(stderr, "[ddpca] rank %d coarse matrix |.| %.17g w %.17g\n", H.rank, c.first, c.second);
     }
     auto solver_guard = solver_lock();
-    rocblas_handle rh = nullptr;
-    if (rocblas_create_handle(&rh) != rocblas_status_success) throw ApiError(DDPCA_EHIP, "rocblas_create_handle");
+    BlasHandle rh(st);
     DevBuf<rocblas_int> info(2);
     info.zero(st);
-    rocblas_set_stream(rh, st);
-    rocblas_status s1, s2;
+    bool accepted;
     if (C.latin) {
         // globCoup (displacements + coarse contact unknowns) is symmetric but indefinite: pivoted
         // LU, then the inverse (symmetric again, so the row-major copy reads it as it is)
         DevBuf<rocblas_int> ipiv(std::max<int64_t>(n, 1));
-        s1 = rocsolver_dgetrf(rh, (rocblas_int)n, (rocblas_int)n, A.p, (rocblas_int)n, ipiv.p, info.p);
-        s2 = rocsolver_dgetri(rh, (rocblas_int)n, A.p, (rocblas_int)n, ipiv.p, info.p + 1);
+        accepted = lu_inverse_device(rh, A.p, n, ipiv.p, info.p);
         DDPCA_HIP(hipStreamSynchronize(st));
     } else {
-        s1 = rocsolver_dpotrf(rh, rocblas_fill_lower, (rocblas_int)n, A.p, (rocblas_int)n, info.p);
-        s2 = rocsolver_dpotri(rh, rocblas_fill_lower, (rocblas_int)n, A.p, (rocblas_int)n, info.p + 1);
-        hipLaunchKernelGGL(k_fill_lower, dim3(std::max<int64_t>(1, ((int64_t)n * n + 255) / 256)), dim3(256), 0, st, A.p, n);
+        accepted = spd_inverse_device(rh, A.p, n, info.p);
     }
     C.ainv.alloc(std::max<int64_t>(C.nown, 1) * n);
     // owned rows are contiguous per subdomain (baseReco blocks)
@@ -1001,9 +986,8 @@ void coarse_invert(ddpca_mcontact& H) {
         k = e + 1;
     }
     DDPCA_HIP(hipStreamSynchronize(st));
-    rocblas_destroy_handle(rh);
     const auto inf = info.download();
-    if (s1 != rocblas_status_success || s2 != rocblas_status_success)
+    if (!accepted)
         throw ApiError(DDPCA_EHIP, "rocsolver potrf/potri failed on globCoup_1");
     if (inf[0] != 0 || inf[1] != 0)
         throw ApiError(DDPCA_ENUMERIC, std::string(C.latin ? "globCoup is singular (getrf" : "globCoup_1 is not positive definite (potrf") +

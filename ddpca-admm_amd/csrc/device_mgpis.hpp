@@ -38,6 +38,7 @@
 
 #include "../../include/ddpca_amd.h"
 #include "device_common.hpp"
+#include "mgpis_bytes.hpp"
 #include "mgpis_plan.hpp"
 #include "sparse.hpp"
 
@@ -228,7 +229,7 @@ public:
     double timed_kernel_bytes = 0.0;  // algorithmic bytes of the sampled launches (active members)
     int64_t timed_kernel_samples = 0;
     bool time_kernel = false;
-    double fine_kernel_bytes(int s) const;  // algorithmic bytes of the timed kernel, member s
+    double fine_kernel_bytes(int s) const { return ddpca::fine_kernel_bytes(bytes_, s); }  // of the timed kernel, member s
     // Algorithmic HBM bytes of the solve path (every input read once, every output
     // written once, gathered operands counted once per unique element), accumulated by pcg_check
     // over the members' iteration counts: [0] fine-level kernels (the Krylov SpMV, k_axpy and the
@@ -237,14 +238,16 @@ public:
     // and the scalar kernels, [2] launches counted
     double alg_bytes[3] = {0.0, 0.0, 0.0};
     // model per member s: one PCG iteration (SpMV + axpy + V-cycle + scalars), split as above;
-    // setup: x0 = 0 initialisation + the first V-cycle
-    void iteration_bytes(int s, double out[2]) const;
-    void setup_bytes(int s, double out[2]) const;
-    void vcycle_bytes(int s, double out[2]) const;
-    int64_t iteration_launches() const;
+    // setup: x0 = 0 initialisation + the first V-cycle (the model itself: mgpis_bytes.cpp)
+    void iteration_bytes(int s, double out[2]) const { ddpca::iteration_bytes(bytes_, s, out); }
+    void setup_bytes(int s, double out[2]) const { ddpca::setup_bytes(bytes_, s, out); }
+    void vcycle_bytes(int s, double out[2]) const { ddpca::vcycle_bytes(bytes_, s, out); }
+    int64_t iteration_launches() const { return ddpca::iteration_launches(bytes_); }
     // operator bytes of one fine pass, member s (prod_cols: with the 16-bit column offsets the
     // production kernels use; the mgpis_gpu_bench_spmv variants read 32-bit columns)
-    double fine_matrix_bytes(int s, int vt, bool prod_cols = true) const;
+    double fine_matrix_bytes(int s, int vt, bool prod_cols = true) const {
+        return ddpca::fine_matrix_bytes(bytes_, s, vt, prod_cols);
+    }
     double bench_spmv(int variant, int reps);  // ms per launch of a fine-level SpMV loop variant
     int64_t graphs_launched = 0;
 
@@ -264,6 +267,7 @@ public:
     void prepare_graphs(int prec) { build_graph(prec); }
 
 private:
+    MgpisBytes bytes_;  // what the byte model reads of this handle (filled by the constructor)
     hipGraphExec_t graph_[2] = {nullptr, nullptr};
     hipGraphExec_t graph_h_[2][kMaxParts] = {};  // [prec][part]
     // one-iteration graphs for the tail of a solve: once the queued iterations reach the members'

@@ -1,6 +1,6 @@
 // Value layout of the streamed SELL-BSR3 operators of MGPIS: what one slot (64 lanes x one 3x3
 // block) looks like in each storage type, and the host-side packing of a block into it.  Read by
-// the kernels (device_mgpis.hip) and by the host plan (mgpis_plan.cpp), so it is plain C++: the
+// the kernels (device_mgpis*.hip) and by the host plan (mgpis_plan.cpp), so it is plain C++: the
 // __host__ __device__ qualifiers sit behind DDPCA_HD and nothing here needs the HIP headers.
 #pragma once
 #include <algorithm>

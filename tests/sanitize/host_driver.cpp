@@ -48,6 +48,7 @@
 #include "common.hpp"
 #include "ddpca_amd.h"
 #include "mass_plan.hpp"
+#include "mgpis_bytes.hpp"
 #include "mgpis_plan.hpp"
 #include "problem.hpp"
 #include "subdomain_ops.hpp"
@@ -1091,9 +1092,222 @@ void plan_general(const MULTIGRID& g) {
                 nlev, (long long)P[L].nloc[0], (long long)nband, (long long)blocks);
 }
 
+// ---- the byte model of the solve path (mgpis_bytes.cpp) on shapes small enough to tally by hand
+MgpisBytes::Level bytes_level(std::vector<int64_t> nloc, std::vector<int64_t> nnzb, std::vector<int64_t> tent) {
+    MgpisBytes::Level L;
+    L.tblk_sub.assign(nloc.size(), 0);
+    L.nloc = std::move(nloc);
+    L.nnzb_sub = std::move(nnzb);
+    L.tent_sub = std::move(tent);
+    return L;
+}
+
+// vcycle_bytes of member s = {fine, below}, iteration_launches = launches (all three literals of the
+// caller's tally), and the identities that tie the other figures to them
+void bytes_check(const MgpisBytes& M, int s, double fine, double below, int64_t launches, const char* what) {
+    double v[2], it[2], su[2];
+    vcycle_bytes(M, s, v);
+    iteration_bytes(M, s, it);
+    setup_bytes(M, s, su);
+    const int64_t nl = iteration_launches(M);
+    if (v[0] != fine || v[1] != below || nl != launches) {
+        std::fprintf(stderr, "FAIL mgpis_bytes: %s member %d: {%.17g, %.17g} and %lld launches, tallied {%.17g, %.17g} and %lld\n",
+                     what, s, v[0], v[1], (long long)nl, fine, below, (long long)launches);
+        ++g_fail;
+    }
+    const double n = (double)M.lev.back().nloc[s], nch = (double)((M.lev.back().nloc[s] + 63) / 64);
+    const bool tied = it[0] == v[0] + fine_kernel_bytes(M, s) + 144.0 * n && it[1] == v[1] + 24.0 * nch &&
+                      su[0] - v[0] == 120.0 * n && su[1] - v[1] == 16.0 * nch &&
+                      fine_kernel_bytes(M, s) == fine_matrix_bytes(M, s, kVal64) + 120.0 * n;
+    if (!tied) {
+        std::fprintf(stderr, "FAIL mgpis_bytes: %s member %d: iteration / setup bytes off the V-cycle's\n", what, s);
+        ++g_fail;
+    }
+}
+
+void byte_model() {
+    // One level (Lf == clev), one member of 5 nodes, fp64 inverse: the dense solve reads the
+    // 15 x 15 inverse (8 * 225 = 1800) and b, writes x (16 * 15 = 240), the dot product reads both
+    // again (240) = 2280, all of it on the "fine" level.  Launches: k_sell<kPcg>, k_fin, k_axpy,
+    // k_fin, k_coarse, k_dot, k_fin = 7
+    {
+        MgpisBytes M;
+        M.lev = {bytes_level({5}, {13}, {0})};
+        bytes_check(M, 0, 2280.0, 0.0, 7, "one level");
+        // the Krylov SpMV: 13 blocks of 72 B + 4 B column, and 5 vectors of 24 B per node
+        pcheck(fine_kernel_bytes(M, 0) == 76.0 * 13 + 120.0 * 5, "one level: fine kernel bytes");
+    }
+
+    // Two levels under block Jacobi: fp64 copies (72 B + 4 B column per block, 9 * 8 = 72 B of inverse
+    // per node), list transfers with stored weights, dense fp64 solve on level 0.  Members (fine
+    // nodes n, coarse nodes c, fine blocks z, stencil entries t): 0 = (5, 2, 11, 7), 1 = (8, 3, 20, 12).
+    // Per launch, nu = 1 (all on the fine level but the coarse solve):
+    //   k_jac0      b in, x out, inverse: (48 + 72) n                  600       960
+    //   residual    76 z + 72 n (x gathered, b, r)                    1196      2096
+    //   restriction r_f 24 n + 12 t + (mask 1 + b_c 24) c              254       411
+    //   coarse      8 (3c)^2 + 16 (3c)              [below]            384       792
+    //   prolongat.  e_c 24 c + (mask 1 + x in/out 48) n + 12 t         377       608
+    //   sweep       76 z + (x, b, x' 72 + inverse 72) n               1556      2672
+    //                                                          fine   3983      6747
+    // launches: the 5 of the recurrence + those 6 = 11.  nu = 2 adds one sweep going down and one
+    // coming up: + 2 * 1556 = 7095, + 2 * 2672 = 12091, 13 launches
+    auto two_level = [] {
+        MgpisBytes M;
+        M.lev = {bytes_level({2, 3}, {4, 9}, {0, 0}), bytes_level({5, 8}, {11, 20}, {7, 12})};
+        M.smoother = 1;
+        return M;
+    };
+    {
+        MgpisBytes M = two_level();
+        bytes_check(M, 0, 3983.0, 384.0, 11, "block Jacobi, nu 1");
+        bytes_check(M, 1, 6747.0, 792.0, 11, "block Jacobi, nu 1");
+        M.nu = 2;
+        bytes_check(M, 0, 7095.0, 384.0, 13, "block Jacobi, nu 2");
+        bytes_check(M, 1, 12091.0, 792.0, 13, "block Jacobi, nu 2");
+        // a member's figures do not move with another member's counts
+        M.lev[1].nloc[1] = 80, M.lev[1].nnzb_sub[1] = 200, M.lev[1].tent_sub[1] = 120, M.lev[0].nloc[1] = 30;
+        bytes_check(M, 0, 7095.0, 384.0, 13, "block Jacobi, nu 2, other member changed");
+        // operator bytes of a fine pass by storage type and column width (11 blocks)
+        M = two_level();
+        pcheck(fine_matrix_bytes(M, 0, kVal64) == 836.0 && fine_matrix_bytes(M, 0, kVal32) == 440.0 &&
+                   fine_matrix_bytes(M, 0, kValH16) == 264.0 && fine_matrix_bytes(M, 0, kValQ8) == 176.0,
+               "fine pass bytes by storage type");
+        M.lev[1].col16 = true;
+        pcheck(fine_matrix_bytes(M, 0, kVal64) == 814.0 && fine_matrix_bytes(M, 0, kVal64, false) == 836.0,
+               "fine pass bytes with 16-bit columns");
+    }
+    // Chebyshev (smoother 2) on member 0: k_jac0 also writes d (+ 24 n = 120), the sweep reads and
+    // writes d (+ 48 n = 240): 3983 + 360 = 4343
+    {
+        MgpisBytes M = two_level();
+        M.smoother = 2;
+        bytes_check(M, 0, 4343.0, 384.0, 11, "Chebyshev, two levels");
+    }
+    // Chebyshev on three levels, one member, (nodes, blocks, stencil entries) = level 0 (1, -, -),
+    // 1 (3, 5, 4), 2 (6, 14, 9): the restriction onto level 1 fuses that level's first sweep
+    //   fine   k_jac0 144 * 6 = 864; residual 76 * 14 + 72 * 6 = 1496; restriction 24 * 6 + 12 * 9 +
+    //          (25 + inverse 72 + x_c 24 + d_c 24) * 3 = 687; prolongation 24 * 3 + 49 * 6 + 12 * 9 = 474;
+    //          sweep 76 * 14 + 192 * 6 = 2216                                              = 5737
+    //   below  residual 76 * 5 + 72 * 3 = 596; restriction 24 * 3 + 12 * 4 + 25 * 1 = 145; coarse
+    //          8 * 9 + 16 * 3 = 120; prolongation 24 * 1 + 49 * 3 + 12 * 4 = 219; sweep 76 * 5 + 192 * 3 = 956
+    //                                                                                      = 2036
+    // launches: 5 + k_jac0 + 2 (residual, restriction) + coarse + 2 (prolongation, sweep) = 15
+    {
+        MgpisBytes M;
+        M.lev = {bytes_level({1}, {1}, {0}), bytes_level({3}, {5}, {4}), bytes_level({6}, {14}, {9})};
+        M.smoother = 2;
+        bytes_check(M, 0, 5737.0, 2036.0, 15, "Chebyshev, three levels");
+    }
+    // Transfer forms against the lists, member 0 above (restriction 254, prolongation 377 of 3983):
+    //   lattice   restriction 24 n + (25 + child mask and fine copy 8) c = 186, prolongation 24 c + 49 n
+    //             + one 4-B word per fine node = 313                                  -> 3851
+    //   uniform   restriction as the lists; prolongation reads 4 B per entry, no weight: 48 + 245 + 28 = 321
+    //                                                                                 -> 3927
+    //   2 block entries: restriction + 32 * 2 + b_c read and written again 24 c = + 112, prolongation
+    //             + 32 * 2 = + 64                                                     -> 4159
+    {
+        MgpisBytes M = two_level();
+        M.lev[1].lat = true;
+        bytes_check(M, 0, 3851.0, 384.0, 11, "lattice transfer");
+        M = two_level();
+        M.lev[1].uw = true;
+        bytes_check(M, 0, 3927.0, 384.0, 11, "uniform-weight transfer");
+        M = two_level();
+        M.lev[1].tblk_sub = {2, 0};
+        bytes_check(M, 0, 4159.0, 384.0, 11, "block transfer entries");
+        bytes_check(M, 1, 6747.0, 792.0, 11, "block transfer entries of the other member");
+    }
+    // Block Jacobi on fp32 iterate copies (x4), nu = 2, member 0 alone: fp32 copy with 16-bit columns
+    // (38 B per block, 418 per pass), fp32 inverses (36 B per node, the dense one 4 B per entry)
+    //   k_jac0 (b 24 + x4 16 + 36) n = 380; sweep 418 + (x4 16 + b 24 + x4' 16 + 36) n = 878; residual
+    //   418 + (16 + 48) n = 738; restriction 254; prolongation 48 + (1 + 32) n + 84 = 297; sweep 878; last
+    //   sweep writes fp64: 418 + (16 + 24 + 24 + 36) n = 918                              = 4343
+    //   coarse 4 * 36 + 16 * 6 = 240
+    {
+        MgpisBytes M;
+        M.lev = {bytes_level({2}, {4}, {0}), bytes_level({5}, {11}, {7})};
+        M.smoother = 1, M.nu = 2, M.ainv32 = true;
+        M.lev[1].vt = kVal32, M.lev[1].col16 = true, M.lev[1].x4 = true;
+        bytes_check(M, 0, 4343.0, 240.0, 13, "block Jacobi on fp32 iterates");
+    }
+
+    // Colour Gauss-Seidel (smoother 3), K = 2 colours, one member: 6 fine and 2 coarse nodes, 8
+    // stencil entries, 10 off-diagonal blocks in the fp32 copy with 16-bit columns (38 B each, 380 per
+    // pass), fp32 inverses (36 B per row and 4 B per dense entry).  x gathered per row: 24 (K - 1) / 2
+    // = 12 by the forward sweep and the residual, 24 (K - 1) = 24 by the backward sweep
+    //   forward     380 + (b 24 + 36 + x 24 + row index 4 + 12) * 6 =  980
+    //   residual    (r 24 + 4 + 12) * 6                             =  240
+    //   restriction 24 * 6 + 12 * 8 + 25 * 2                        =  290
+    //   coarse      4 * 36 + 16 * 6                         [below] =  240
+    //   prolongat.  24 * 2 + (1 + 48) * 6 + 12 * 8                  =  438
+    //   backward    380 + (24 + 36 + 24 + 4 + 24) * 6               = 1052     fine = 3000
+    // launches: 5 + 2 forward + residual + restriction + coarse + prolongation + 2 backward = 13
+    auto colours = [] {
+        MgpisBytes M;
+        M.lev = {bytes_level({2}, {4}, {0}), bytes_level({6}, {40}, {8})};
+        M.lev[1].vt = kVal32, M.lev[1].col16 = true;
+        M.smoother = 3, M.ainv32 = true;
+        M.gs.ncol = 2, M.gs.vt = kVal32, M.gs.col16 = true;
+        M.gs.nnzb_sub = {10};
+        return M;
+    };
+    {
+        MgpisBytes M = colours();
+        bytes_check(M, 0, 3000.0, 240.0, 13, "colour Gauss-Seidel");
+        // band mode: 4 band rows, 1 ring row with 3 band blocks, 1 far row
+        //   x = 0, r = b outside the colours 76 * 2 = 152; forward 380 + 100 * 4 = 780; residual 40 * 4 =
+        //   160; the ring's residual 38 * 3 + 76 * 1 = 190; restriction 290; prolongation 438; backward
+        //   380 + 112 * 4 = 828; b . x outside the colours 52 * 2 = 104                   = 2942
+        // launches: + the three launches outside the colours = 16
+        M.gs.band = true;
+        M.gs.band_rows_sub = {4}, M.gs.ring_rows_sub = {1}, M.gs.far_rows_sub = {1}, M.gs.ring_nnzb_sub = {3};
+        bytes_check(M, 0, 2942.0, 240.0, 16, "colour Gauss-Seidel, band mode");
+        // fp32 iterate and residual copies (x4, r4: 16 B where 24 B was) with the lattice transfer they need
+        //   forward 380 + (24 + 36 + 16 + 4 + 8) * 6 = 908; residual (16 + 4 + 8) * 6 = 168; restriction
+        //   16 * 6 + (25 + 8) * 2 = 162; prolongation 24 * 2 + (1 + 32) * 6 + 4 * 6 = 270; backward 380 +
+        //   (24 + 36 + z 24 + x4 16 + 4 + 16) * 6 = 1100                                  = 2608
+        // the residual left in fp64 (x4 only): residual (24 + 4 + 8) * 6 = 216, restriction 24 * 6 + 66 =
+        //   210                                                                           = 2704
+        M = colours();
+        M.lev[1].lat = true, M.gs.x4 = true, M.gs.r4 = true;
+        bytes_check(M, 0, 2608.0, 240.0, 13, "colour Gauss-Seidel on fp32 iterates and residual");
+        M.gs.r4 = false;
+        bytes_check(M, 0, 2704.0, 240.0, 13, "colour Gauss-Seidel on fp32 iterates");
+    }
+    // Colour SSOR (smoother 4) on the same shape: L and U passes of 190 each
+    //   forward from zero  190 + (b 24 + 36 + x 24 + w 24 + 4 + 12) * 6 =  934
+    //   backward           190 + (b, w 48 + 36 + x 24 + 4 + 12) * 6     =  934
+    //   residual           190 + (w 24 + r 24 + 4 + 12) * 6             =  574
+    //   restriction 290, prolongation 438
+    //   forward            380 + (24 + 36 + 24 + 24 + 4 + 24) * 6       = 1196
+    //   backward           190 + (48 + 36 + z 24 + 4 + 12) * 6          =  934     fine = 5300
+    // launches: 5 + (2 + 2 + 1) + restriction + coarse + prolongation + (2 + 2) = 17
+    {
+        MgpisBytes M = colours();
+        M.smoother = 4;
+        bytes_check(M, 0, 5300.0, 240.0, 17, "colour SSOR");
+    }
+
+    // Table mode: a fine pass reads 4 B per block and per node and the member's share of the table
+    // by nodes -- 3 row types of 27 doubles = 648 B over 4 + 12 nodes: 162 and 486, which sum to
+    // the table; the share is the one figure that moves with another member's count
+    {
+        MgpisBytes M;
+        M.lev = {bytes_level({1, 1}, {1, 1}, {0, 0}), bytes_level({4, 12}, {9, 30}, {0, 0})};
+        M.lev[1].tbl = true, M.lev[1].ntypes = 3, M.lev[1].tstride = 27;
+        const double a = fine_matrix_bytes(M, 0, kVal64), b = fine_matrix_bytes(M, 1, kVal64);
+        pcheck(a == 36.0 + 16.0 + 162.0 && b == 120.0 + 48.0 + 486.0, "table mode: fine pass bytes");
+        pcheck((a - 52.0) + (b - 168.0) == 648.0, "table mode: the shares sum to the table");
+        M.lev[1].nloc[1] = 4;
+        pcheck(fine_matrix_bytes(M, 0, kVal64) == 36.0 + 16.0 + 324.0, "table mode: the share follows the node total");
+    }
+    std::printf("{\"case\": \"mgpis_bytes\", \"tallies\": 18}\n");
+}
+
 void run_mgpis_plan() {
     plan_levels_and_records();
     plan_transfers_and_colours();
+    byte_model();
 }
 
 // ---- the ADMM handle's host setup (admm_plan.cpp), called directly on established problems

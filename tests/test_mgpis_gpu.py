@@ -341,7 +341,7 @@ import scipy.sparse as sp
 sys.path.insert(0, sys.argv[1])
 D = importlib.import_module("ddpca-admm_amd")
 # one problem per thread (no host state shared), the whole fine level as the V-cycle's exact level:
-# a dense SPD inverse of 4,455 - 165 rows by rocSOLVER potrf + potri (device_mgpis.hip
+# a dense SPD inverse of 4,455 - 165 rows by rocSOLVER potrf + potri (device_dense.hip
 # invert_spd_device), the size class of the r04b failures (n = 3468)
 probs = [D.Problem("beam", 16, 4, 2, 1, 1, 1, 1).ESTABLISH() for _ in range(5)]
 n = len(probs[0].grid(0).consForc)

@@ -8,7 +8,8 @@ the C ABI (problems of every generator incl. rank-local builds, a refined curved
 search, the refused-argument paths) and, called directly, the surface-mass batch's host setup
 (mass_plan.cpp: packing, pairing, spectrum bounds, Chebyshev step counts) and the host setup of an MGPIS
 device handle (mgpis_plan.cpp, run_mgpis_plan and plan_general in the driver: level packing, value records,
-transfers, colours, coarse packing on the smallest shapes at which each can go wrong) and the host setup of
+transfers, colours, coarse packing on the smallest shapes at which each can go wrong; the solve path's byte
+model and launch count, mgpis_bytes.cpp, against per-launch tallies written out by hand) and the host setup of
 the ADMM handle (admm_plan.cpp, run_admm_plan and admm_plan_octree in the driver: the workspace layout, every
 SELL-64 interface operator and the coupling / hanging rows against term-by-term products within
 (k - 1) eps sum |terms|, both branches of the fused decision, the coarse right-hand side's slots of two-rank
