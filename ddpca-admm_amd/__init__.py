@@ -209,6 +209,13 @@ def _declare(L: C.CDLL) -> None:
     L.ddpca_problem_set_galerkin_device.argtypes = [_P, C.c_int]
     L.ddpca_galerkin_last_ms.argtypes = [_DP]
     L.ddpca_galerkin_last_level_ms.argtypes = [_DP, C.c_int64]
+    L.ddpca_interface_build_on.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int64,
+                                           _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.POINTER(_P)]
+    L.ddpca_interface_view.argtypes = [_P, C.c_char_p, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    L.ddpca_interface_destroy.argtypes = [_P]
+    L.ddpca_problem_set_mortar_device.argtypes = [_P, C.c_int]
+    L.ddpca_mortar_last_ms.argtypes = [_DP]
+    L.ddpca_problem_set_ips_from.argtypes = [_P, C.c_int64, _P, C.c_double, C.c_double, C.c_double]
     L.mgpis_gpu_vcycle.argtypes = [_P, _P, _P]
     L.mgpis_gpu_batch_vcycle.argtypes = [_P, _P, _P, _P]
     L.mgpis_gpu_batch_solve.argtypes = [_P, _P, _P, C.c_int, C.c_double, _P, C.c_int, _P, _P, _P]
@@ -362,6 +369,11 @@ class Problem:
         _check(lib().ddpca_problem_set_ips(self._h, ts, len(gap), _ptr(node), _ptr(shap), _ptr(basis), _ptr(gap),
                                            _ptr(w), fric, penN, penF))
 
+    def set_ips_from(self, ts: int, ips: "Ips", fric: float, penN: float, penF: float) -> None:
+        """set_ips straight from a search result's handle (contact_search_ips), without the copy of
+        216 B per point through caller arrays (ddpca_problem_set_ips_from)."""
+        _check(lib().ddpca_problem_set_ips_from(self._h, ts, ips.handle, fric, penN, penF))
+
     def set_coarse(self, muscSett: int, doleMcsc: Optional[Sequence[int]] = None) -> "Problem":
         """MCONTACT::muscSett / doleMcsc (MCONTACT.h:22-23) before ESTABLISH; 2 = the
         interface-eliminated coarse space (MULTISCALE_1)."""
@@ -371,12 +383,15 @@ class Problem:
         return self
 
     def ESTABLISH(self, owner: Optional[Sequence[int]] = None, rank: int = 0, assembly_device: int = -1,
-                  galerkin_device: int = -1) -> "Problem":
+                  galerkin_device: int = -1, mortar_device: int = -1) -> "Problem":
         """MCONTACT::ESTABLISH; with owner/rank only this rank's subdomains are built.
         assembly_device >= 0: STIF_MATR of every owned subdomain on that GPU
         (ddpca_problem_set_assembly_device); -1: the host loop.  galerkin_device >= 0: the Galerkin
         chain of every owned subdomain's CONSTRAINT on that GPU (ddpca_problem_set_galerkin_device);
-        -1: galerkin_rap on the host."""
+        -1: galerkin_rap on the host.  mortar_device >= 0: the mortar operators of every owned
+        interface (Interface::BUILD) on that GPU (ddpca_problem_set_mortar_device); -1: the host loop."""
+        if mortar_device >= 0:
+            _check(lib().ddpca_problem_set_mortar_device(self._h, int(mortar_device)))
         if assembly_device >= 0:
             _check(lib().ddpca_problem_set_assembly_device(self._h, int(assembly_device)))
         if galerkin_device >= 0:
@@ -541,22 +556,48 @@ def contact_search(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, b
     (n, 2, 4), shap (n, 2, 4), basis (n, 3, 3), gap (n), w (n) -- Problem.set_ips' arguments.
     device: None, the host search (ddpca_contact_search); an int, ddpca_contact_search_on -- a GPU
     index, -1 (the same host search) or -2 (the device path's steps on the host)."""
+    return contact_search_ips(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck, maxiDist, device).get()
+
+
+class Ips:
+    """A search result kept in the library (ddpca_ips_t): Problem.set_ips_from takes it as it is."""
+
+    def __init__(self, handle: C.c_void_p):
+        self._h = handle
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.ddpca_ips_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self) -> C.c_void_p:
+        return self._h
+
+    def __len__(self) -> int:
+        return int(lib().ddpca_ips_count(self._h))
+
+    def get(self) -> dict:
+        n = len(self)
+        out = dict(node=np.empty((n, 2, 4), np.int64), shap=np.empty((n, 2, 4)), basis=np.empty((n, 3, 3)),
+                   gap=np.empty(n), w=np.empty(n))  # ddpca_ips_get writes every element
+        if n:
+            _check(lib().ddpca_ips_get(self._h, _ptr(out["node"]), _ptr(out["shap"]), _ptr(out["basis"]), _ptr(out["gap"]),
+                                       _ptr(out["w"])))
+        return out
+
+
+def contact_search_ips(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck, maxiDist: float = 1.0e12,
+                       device=None) -> Ips:
+    """contact_search, the result left in the library as an Ips handle (for Problem.set_ips_from)."""
     args, keep = _csearch_args(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck)
     h = C.c_void_p()
     if device is None:
         _check(lib().ddpca_contact_search(*args, float(maxiDist), C.byref(h)))
     else:
         _check(lib().ddpca_contact_search_on(int(device), *args, float(maxiDist), C.byref(h)))
-    try:
-        n = int(lib().ddpca_ips_count(h))
-        out = dict(node=np.empty((n, 2, 4), np.int64), shap=np.empty((n, 2, 4)), basis=np.empty((n, 3, 3)),
-                   gap=np.empty(n), w=np.empty(n))  # ddpca_ips_get writes every element
-        if n:
-            _check(lib().ddpca_ips_get(h, _ptr(out["node"]), _ptr(out["shap"]), _ptr(out["basis"]), _ptr(out["gap"]),
-                                       _ptr(out["w"])))
-        return out
-    finally:
-        lib().ddpca_ips_destroy(h)
+    return Ips(h)
 
 
 def refine_select(mast_xyz, mast_segm, mast_2d, slav_xyz, slav_segm, slav_2d, buck, distCrit: float, mast_elem, slav_elem,
@@ -1156,6 +1197,74 @@ def galerkin_last_level_ms() -> tuple:
     return tuple(out[:n])
 
 
+class InterfaceOperators:
+    """The result of interface_build (ddpca_interface_t): the nine mortar operators of each side and
+    the interface's vectors, read through ddpca_interface_view."""
+    OPS = ("systMass", "systTran", "systTran_pena", "inteMass", "inteMass_pena", "inpoLagr", "inpoDisp", "inteInpo",
+           "pemaInpo_r")
+
+    def __init__(self, handle: C.c_void_p):
+        self._h = handle
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and _lib is not None:
+            _lib.ddpca_interface_destroy(h)
+            self._h = None
+
+    def array(self, name: str, side: int = 0) -> np.ndarray:
+        data, count, dt = C.c_void_p(), C.c_int64(), C.c_int()
+        _check(lib().ddpca_interface_view(self._h, name.encode(), int(side), C.byref(data), C.byref(count), C.byref(dt)))
+        dtype = np.dtype(_DTYPES[dt.value])
+        if count.value == 0:
+            return np.zeros(0, dtype)
+        buf = (C.c_char * (count.value * dtype.itemsize)).from_address(data.value)
+        return np.frombuffer(buf, dtype=dtype).copy()
+
+    def csr(self, name: str, side: int = 0):
+        import scipy.sparse as sp
+        return sp.csr_matrix((self.array(f"{name}:val", side), self.array(f"{name}:col", side), self.array(f"{name}:ptr", side)),
+                             shape=tuple(self.array(f"{name}:shape", side)))
+
+    @property
+    def factored(self) -> bool:
+        return bool(self.array("factored")[0])
+
+
+def interface_build(nn0: int, nn1: int, node, shap, basis, gap, w, fric: float, penN: float, penF: float, rot0=None,
+                    rot1=None, device: int = -1) -> InterfaceOperators:
+    """Interface::BUILD (MCONTACT.h:181-810, CONT_ROTA 157-179) on the caller's points (set_ips'
+    arrays) for bodies of nn0 / nn1 nodes; rot0 / rot1: (node ids, (n, 3, 3) rotations) or None.
+    device: a GPU index (the kernels of device_mortar.hip), -1 (Interface::BUILD on the host) or -2
+    (the device path's steps on the host) -- ddpca_interface_build_on."""
+    node = np.ascontiguousarray(node, dtype=np.int64).reshape(-1)
+    shap = np.ascontiguousarray(shap, dtype=np.float64).reshape(-1)
+    basis = np.ascontiguousarray(basis, dtype=np.float64).reshape(-1)
+    gap = np.ascontiguousarray(gap, dtype=np.float64).reshape(-1)
+    w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+    rots = []
+    for r in (rot0, rot1):
+        rn = np.ascontiguousarray([] if r is None else r[0], dtype=np.int64).reshape(-1)
+        rm = np.ascontiguousarray(np.zeros((0, 3, 3)) if r is None else r[1], dtype=np.float64).reshape(-1)
+        if len(rm) != 9 * len(rn):
+            raise ValueError("a rotation is 3 x 3 per listed node")
+        rots += [len(rn), _ptr(rn), _ptr(rm)]
+        rots.append((rn, rm))  # keeps the arrays alive until the call returns
+    h = C.c_void_p()
+    _check(lib().ddpca_interface_build_on(int(device), int(nn0), int(nn1), float(fric), float(penN), float(penF), len(gap),
+                                          _ptr(node), _ptr(shap), _ptr(basis), _ptr(gap), _ptr(w), *rots[0:3], *rots[4:7],
+                                          C.byref(h)))
+    return InterfaceOperators(h)
+
+
+def mortar_last_ms() -> tuple:
+    """Of this thread's last device build of mortar operators, in ms: plan, uploads and allocations,
+    k_mortar_pair, k_mortar_nodal + k_mortar_ip, copy back (ddpca_mortar_last_ms; measurement only)."""
+    out = (C.c_double * 5)()
+    _check(lib().ddpca_mortar_last_ms(out))
+    return tuple(out)
+
+
 def mass_solve(systems: Sequence, b: np.ndarray, rtol: float = 1e-14, maxit: int = 2000, fuse_alpha: int = -1,
                device: int = 0):
     """The ADMM loop's batched surface-mass Jacobi-PCG on its own (ddpca_mass_solve): systems = square
@@ -1330,7 +1439,8 @@ class MCONTACT:
 
 
 __all__ = ["Problem", "MULTIGRID", "TreeMultigrid", "write_resuStre", "write_resuFreq", "MGPIS", "MCONTACT", "DdpcaError", "lib", "gpu_available", "default_options",
-           "contact_search", "refine_select", "csearch_last_ms", "csearch_last_pairs", "mass_solve", "stream_ceiling", "probe_grid_barrier",
+           "contact_search", "refine_select", "csearch_last_ms", "csearch_last_pairs", "contact_search_ips", "Ips",
+           "interface_build", "InterfaceOperators", "mortar_last_ms", "mass_solve", "stream_ceiling", "probe_grid_barrier",
            "LIBPATH", "HEADLINE_OPTIONS", "HEADLINE_OPTIONS_SMALL", "headline_options", "HEADLINE_MUSC",
            "HEADLINE_WORKLOAD",
            "headline_problem"]

@@ -16,9 +16,15 @@ namespace ddpca {
 
 
 void Interface::BUILD(const MULTIGRID& g0, const MULTIGRID& g1) {
+    const int64_t nn[2] = {g0.numNodes(), g1.numNodes()};
+    const NodeRota* const rot[2] = {&g0.nodeRota, &g1.nodeRota};
+    BUILD(nn, rot);
+}
+
+void Interface::BUILD(const int64_t nnode[2], const NodeRota* const nodeRota[2]) {
     const int C = comp();
     const int64_t nip = (int64_t)ip.size();
-    const MULTIGRID* g[2] = {&g0, &g1};
+    static const NodeRota noRota;
     const double pen[3] = {penN, penF, penF};
 #pragma omp parallel for schedule(static, 1) num_threads(2)
     for (int s = 0; s < 2; ++s) {
@@ -27,7 +33,7 @@ void Interface::BUILD(const MULTIGRID& g0, const MULTIGRID& g1) {
         for (const auto& p : ip)
             for (int k = 0; k < 4; ++k)
                 if (nc.emplace(p.node[s][k], (int64_t)nc.size()).second) nodeCont[s].push_back(p.node[s][k]);
-        const int64_t nn = g[s]->numNodes();
+        const int64_t nn = nnode[s];
         const int64_t ncn = (int64_t)nodeCont[s].size();
         const int64_t mc = C * ncn;
         // ---- contact-node pairs coupled by an integration point (node-block sparsity)
@@ -228,7 +234,7 @@ void Interface::BUILD(const MULTIGRID& g0, const MULTIGRID& g1) {
     // per-ip form (its rows are no longer outer products of the shape values and the basis).
     factored = true;
     for (int s = 0; s < 2; ++s) {
-        const auto& rot = g[s]->nodeRota;
+        const NodeRota& rot = nodeRota[s] ? *nodeRota[s] : noRota;
         if (rot.empty()) continue;
         bool any = false;
         for (int64_t n : nodeCont[s]) any = any || rot.count(n);
@@ -302,10 +308,23 @@ void MCONTACT::ESTABLISH(const std::vector<uint8_t>* owned) {
             for (auto& ip : searCont[ts].ip)
                 for (int k = 0; k < 4; ++k) ip.node[s][k] = pos.at(ip.node[s][k]);
         }
+    if (mortarBy) {
+        // the device assembly of the mortar operators (mortarBy): one interface after the other on
+        // the one GPU
+        for (int64_t ts = 0; ts < nint; ++ts) {
+            Interface& itf = searCont[ts];
+            if (!mine(itf.body[0]) && !mine(itf.body[1])) continue;
+            const MULTIGRID &g0 = multGrid[itf.body[0]], &g1 = multGrid[itf.body[1]];
+            const int64_t nn[2] = {g0.numNodes(), g1.numNodes()};
+            const NodeRota* const rot[2] = {&g0.nodeRota, &g1.nodeRota};
+            mortarBy(itf, nn, rot);
+        }
+    } else {
 #pragma omp parallel for schedule(dynamic, 1)
-    for (int64_t ts = 0; ts < nint; ++ts) {
-        Interface& itf = searCont[ts];
-        if (mine(itf.body[0]) || mine(itf.body[1])) itf.BUILD(multGrid[itf.body[0]], multGrid[itf.body[1]]);
+        for (int64_t ts = 0; ts < nint; ++ts) {
+            Interface& itf = searCont[ts];
+            if (mine(itf.body[0]) || mine(itf.body[1])) itf.BUILD(multGrid[itf.body[0]], multGrid[itf.body[1]]);
+        }
     }
     // the device assembly (stifValues): one subdomain after the other on the one GPU, before the
     // host threads share out the rest

@@ -11,6 +11,8 @@
 
 namespace ddpca {
 
+using NodeRota = std::map<int64_t, std::array<double, 9>>;  // MULTIGRID::nodeRota
+
 // CSEARCH::INTEGRAL_POINT (CSEARCH.h:19-32): the setup-time data contract of one interface.
 struct IntegralPoint {
     int64_t node[2][4];
@@ -40,6 +42,9 @@ struct Interface {
     // may apply them in that factored form (operators handed over by a caller are not assumed so)
     bool factored = false;
     void BUILD(const MULTIGRID& g0, const MULTIGRID& g1);
+    // the same from what BUILD reads of the two bodies: their node counts and nodal rotations
+    // (null: none); the MULTIGRID form forwards here
+    void BUILD(const int64_t nn[2], const NodeRota* const nodeRota[2]);
 };
 
 // Interface-eliminated coarse space (MCONTACT::MULTISCALE_1, MCONTACT.h:1672-2301).  Built
@@ -99,6 +104,9 @@ public:
     // set (ddpca_problem_set_galerkin_device): every owned subdomain's CONSTRAINT leaves its
     // Galerkin chain to it (MULTIGRID::galerkinChain), from ESTABLISH's loop over the subdomains
     GalerkinChain galerkinBy;
+    // set (ddpca_problem_set_mortar_device): ESTABLISH builds every owned interface's mortar
+    // operators through it, one after the other, in place of the OpenMP loop over Interface::BUILD
+    std::function<void(Interface&, const int64_t nn[2], const NodeRota* const nodeRota[2])> mortarBy;
     double GET_CHAR_LENG() const;  // MCONTACT.h:2478-2491
 };
 

@@ -302,6 +302,56 @@ int ddpca_refine_select_on(int device, const double* mast_xyz, int64_t mast_nnod
  * emit, the others 0.  out3: candidate pairs, kept pairs, points. */
 int ddpca_csearch_last_ms(double* out5);
 int64_t ddpca_csearch_last_pairs(int64_t* out3);
+/* Interface::BUILD of MCONTACT::ESTABLISH (MCONTACT.h:181-810, CONT_ROTA 157-179) on points of the
+ * caller, on a chosen path: the nine mortar operators of each side (systMass, systTran,
+ * systTran_pena, inteMass, inteMass_pena, inpoLagr, inpoDisp, inteInpo, pemaInpo_r), nodeCont,
+ * inpoNgap, pemaDiag and `factored`.
+ *   nn0, nn1                    node counts of the two bodies
+ *   fric, penN, penF            fricCoef (0: one component per point, else three) and the penalties
+ *   node .. w                   nip points in ddpca_problem_set_ips's layout
+ *   nrot, rot_node, rot (x 2)   the bodies' nodal rotations in ddpca_write_resuDisp's layout:
+ *                               row-major 3x3 per listed node
+ *   device >= 0  the values on that GPU.  The host builds the plan (every index of BUILD: the
+ *                patterns, the incidence list that fixes the order of the sums, the two sort
+ *                permutations per point); k_mortar_pair sums every contact-node pair in the host's
+ *                order, k_mortar_nodal and k_mortar_ip write the values at the plan's positions.  No
+ *                atomics; two runs return identical bytes; patterns identical to the host's and the
+ *                values equal to its bits (same operations, same order, no contraction).  Every
+ *                device buffer lives for the call; a failed allocation is DDPCA_EHIP with what was
+ *                being allocated and its size.  No host fallback: no gfx950 is DDPCA_ENOGPU.
+ *   device = -1  Interface::BUILD on the host, unchanged.
+ *   device = -2  the device path's own steps on the host: its plan and the kernels' thread bodies
+ *                (mortar_point.hpp) in the kernels' order, OpenMP.  It exists so that everything but
+ *                the launch can be tested and sanitized without a GPU.
+ * DDPCA_EINVAL before anything is launched: a node id outside [0, nn), and on the planned paths any
+ * count or offset the int32 col arrays or the kernels' int32 indices cannot hold. */
+typedef struct ddpca_interface* ddpca_interface_t;
+int ddpca_interface_build_on(int device, int64_t nn0, int64_t nn1, double fric, double penN, double penF, int64_t nip,
+                             const int64_t* node, const double* shap, const double* basis, const double* gap,
+                             const double* w, int64_t nrot0, const int64_t* rot_node0, const double* rot0, int64_t nrot1,
+                             const int64_t* rot_node1, const double* rot1, ddpca_interface_t* out);
+/* MCONTACT.h:181-810, 157-179: read-only view of one array of the result (dtype codes of
+ * ddpca_problem_view).  Names as ddpca_problem_view's interface-side arrays: "systMass:ptr|col|val|
+ * shape" ... "pemaInpo_r:...", "nodeCont" (with `side` 0 or 1), "inpoNgap", "pemaDiag", and "factored"
+ * (one int64; side ignored for the last three).  An unknown name is DDPCA_EINVAL. */
+int ddpca_interface_view(ddpca_interface_t h, const char* name, int side, const void** data, int64_t* count, int* dtype);
+/* MCONTACT.h:181-810, 157-179 */
+int ddpca_interface_destroy(ddpca_interface_t h);
+/* MCONTACT.h:181-810, 157-179, from MCONTACT::ESTABLISH (812-825), called before
+ * ddpca_problem_establish(_owned): device >= 0 builds the owned interfaces' mortar operators on that
+ * GPU (the path of ddpca_interface_build_on), one interface after the other after the renumbering
+ * of general trees, in place of the OpenMP loop over Interface::BUILD; it fills the same members.
+ * device < 0 (the default): the host loop.  DDPCA_ESTATE once the problem is established. */
+int ddpca_problem_set_mortar_device(ddpca_problem_t p, int device);
+/* MCONTACT.h:181-810, 157-179 (measurement only): of the calling thread's last device build, in ms:
+ * the plan on the host, uploads and allocations (host clock), k_mortar_pair, k_mortar_nodal +
+ * k_mortar_ip (HIP events, both sides), the copy back (host clock). */
+int ddpca_mortar_last_ms(double* out5);
+/* Hands a search result to interface ts of the problem straight from the handle (the points
+ * Interface::BUILD reads, MCONTACT.h:181-810; CSEARCH.h:19-32): ddpca_ips_get into caller arrays
+ * followed by ddpca_problem_set_ips, without the caller's copy of 216 B per point.  Host-only.
+ * DDPCA_ESTATE after establish, or for a handle that kept the node ids only. */
+int ddpca_problem_set_ips_from(ddpca_problem_t p, int64_t ts, ddpca_ips_t h, double fric, double penN, double penF);
 /* Coarse-space setting of MCONTACT (muscSett / doleMcsc, MCONTACT.h:22-23), before establish.
  * muscSett = 2 selects the interface-eliminated coarse space (MULTISCALE_1, MCONTACT.h:
  * 1672-2301; the examples' choice, e.g. BLOCK.h:38, TORSION.h:39, DEHW.h:2222), built by
